@@ -2,8 +2,16 @@
 """bench.py -- Msamples/s of the HIP path tracer on the 1280x960 reference Cornell
 scene (BASELINE.json metric / configs[1]: 2048 spp, one frame per step).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
+
+A plain run sets up, renders the W warm-up and K timed frames of the one config,
+writes the last frame if asked (--dump-outputs DIR: DIR/image.npy, the H x W x 4
+float64 RGBA frame rank 0 holds after the last timed step; scene records and seeds
+are fixed, so two builds can be compared frame for frame) and prints the result
+line with the roofline of the timed launches.  `--full` adds the measurements that
+take runs of their own: the CPU baseline, the PCIe-inclusive ptmi_trace call, the
+other configurations (--extra) and the statistical-RNG frames.
 
 `--gpus N` with N > 1 and no torch.distributed environment starts the N ranks
 itself (one child process per GPU, LOCAL_RANK 0..N-1, before this process touches
@@ -32,7 +40,7 @@ per launch from rocprofv3 PMC passes of this build (they cannot run inside this
 process; profiles/pmc_measured.json freezes them from profiles/<round>/).
 cpu_baseline: the oracle's C restatement of the reference kernel (OpenMP) timed on
 the host cores on a bounded sample of the same frame spread over its sample
-indices, plus the whole C1 frame (rank 0, N=1 only).
+indices, plus the whole C1 frame (rank 0, N=1 only; --full).
 """
 import argparse
 import json
@@ -209,12 +217,17 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--samples", type=int, default=0, help="override spp (0 = config)")
     ap.add_argument("--chunks", type=int, default=0)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame of the last timed step (rank 0) as DIR/image.npy (H x W x 4 float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: CPU baseline, the ptmi_trace call, the --extra "
+                         "configs and the statistical-RNG frames (a plain run times the one config only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-trace-call", action="store_true", help="skip the PCIe-inclusive ptmi_trace timing")
     ap.add_argument("--save-image", default="")
     ap.add_argument("--extra", default="auto",
-                    help="other configs timed after the headline at the same GPU count: a comma list, none, or "
-                         "auto (c3,c5 after a default c2 run at full spp)")
+                    help="with --full: other configs timed after the headline at the same GPU count: a comma "
+                         "list, none, or auto (c3,c4,c5 after a default c2 run at full spp)")
     ap.add_argument("--extra-steps", type=int, default=2)
     ap.add_argument("--rng", default="noise3d", choices=("noise3d", "xoshiro"),
                     help="xoshiro: the headline config in the opt-in statistical RNG mode (profiling; not `value`)")
@@ -272,7 +285,7 @@ def main():
     comm = {"backend": dist.get_backend() if world > 1 else "none", "world_size": world,
             "distinct_devices": len({r["uuid"] or r["pci"] for r in ranks_info}), "ranks": ranks_info}
 
-    def run_config(cfg, steps, warmup, samples=0, chunks=0, save_image="", rng=0):
+    def run_config(cfg, steps, warmup, samples=0, chunks=0, save_image="", rng=0, dump_outputs=""):
         """Render `steps` timed frames of config `cfg` on this rank's share (after
         `warmup` untimed ones): barrier + synchronize on both sides, max over ranks.
         Returns (per-config results on rank 0, the scene inputs)."""
@@ -344,6 +357,9 @@ def main():
             ok = bool(torch.isfinite(im).all().item()) and bool((im[..., 3] == 1.0).all().item())
             if save_image:
                 np.save(save_image, im.cpu().numpy())
+            if dump_outputs:  # what the caller of the timed path holds after its last step
+                os.makedirs(dump_outputs, exist_ok=True)
+                np.save(os.path.join(dump_outputs, "image.npy"), im.cpu().numpy())
             avg_ms = float(per_rank[0, 1])
             my_samples_per_launch = npix * (s1 - s0) if split == "sample" else W * H * S / max(world, 1)
             par = "single GPU"
@@ -463,7 +479,8 @@ def main():
 
     res, (objs, tris, grps, cam, S, seeds_host) = run_config(args.config, args.steps, args.warmup, args.samples,
                                                              args.chunks, args.save_image,
-                                                             rng=api.RNG_XOSHIRO if args.rng == "xoshiro" else 0)
+                                                             rng=api.RNG_XOSHIRO if args.rng == "xoshiro" else 0,
+                                                             dump_outputs=args.dump_outputs)
     # The other BASELINE configurations at this GPU count, after the headline frames
     # (C3 / C5 are the reference's 8-GPU configurations; the driver's 1/2/4/8 runs then
     # measure their scaling too).  Secondary: `value` and `ms_per_step` are the headline's.
@@ -472,7 +489,7 @@ def main():
     # config, reported under its own key: its images are not the reference's, so it is
     # never `value`.
     stat_rng = None
-    if args.extra == "auto" and args.config == "c2" and not args.samples and not args.chunks:
+    if args.full and args.extra == "auto" and args.config == "c2" and not args.samples and not args.chunks:
         r, _ = run_config("c2", args.extra_steps, 1, rng=api.RNG_XOSHIRO)
         if rank == 0:
             stat_rng = {"value": round(r["value"], 2), "unit": "Msamples/s", "ms_per_step": round(r["ms_per_step"], 3),
@@ -481,7 +498,7 @@ def main():
                         "what": "C2 with the opt-in statistical RNG (xoshiro128** per path instead of the "
                                 "reference's noise3D): converges to the same image, does not equal it "
                                 "(tests/test_gpu_rng_mode.py); not comparable to `value`"}
-    extra = args.extra
+    extra = args.extra if args.full else "none"
     if extra == "auto":
         extra = "c3,c4,c5" if args.config == "c2" and not args.samples and not args.chunks else "none"
     for cfg in [c for c in extra.split(",") if c and c != "none" and c != args.config]:
@@ -504,14 +521,14 @@ def main():
         el = res["ms_per_step"] * args.steps / 1e3
         roof = roofline(res)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(layout, objs, tris, grps, cam, S, seeds_host)
         # The drop-in call as the Go side makes it (host records and seeds in, host RGBA
         # out: scene conversion + BVH build, PCIe transfers, kernels): one frame.  The
         # bench contract fixes `value` to the HBM-resident rate; this is the rate the
         # Go caller of ocl.Trace sees (SURVEY.md 8d t_trace).
         inclusive = None
-        if world == 1 and not args.no_trace_call:
+        if args.full and world == 1 and not args.no_trace_call:
             api.Trace(objs, tris, grps, device, S, cam, seeds=seeds_host)  # warm-up: host page-in, allocator
             t0 = time.perf_counter()
             api.Trace(objs, tris, grps, device, S, cam, seeds=seeds_host)
@@ -522,6 +539,7 @@ def main():
         line = {
             "metric": "Msamples/sec (1280x960 ref scene)", "value": round(value, 2), "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3),
+            "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "data": "synthetic: restated reference scene records, PCG64 per-pixel seeds",
             "config": res["config"],

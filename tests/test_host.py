@@ -16,7 +16,7 @@ from tests.scene_inputs import MESH_SCENES, scene_inputs
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 LIB = os.path.join(ROOT, "pathtracer-ocl_amd", "build", "libptmi_host.so")
-ASSETS = scenes.ASSETS
+PACKED = os.path.join(ROOT, "tests", "golden", "assets")  # teapot.obj.xz, gopher.obj.xz, gopher.mtl.xz (mesh fixtures)
 
 
 class Records(ctypes.Structure):
@@ -40,7 +40,18 @@ def lib():
     return lib
 
 
-def _build(lib, name, w, h, ap=0.0, fl=0.0, assets=ASSETS):
+@pytest.fixture(scope="module")
+def assets(tmp_path_factory):
+    """The OBJ / MTL meshes, unpacked from tests/golden/assets/*.xz into a directory of their own."""
+    import lzma
+    d = tmp_path_factory.mktemp("assets")
+    for f in sorted(os.listdir(PACKED)):
+        with lzma.open(os.path.join(PACKED, f)) as src:
+            (d / f[:-3]).write_bytes(src.read())
+    return str(d)
+
+
+def _build(lib, name, w, h, ap=0.0, fl=0.0, assets="assets"):
     r = Records()
     err = ctypes.create_string_buffer(512)
     rc = lib.ptmi_host_build_scene(name.encode(), w, h, ap, fl, assets.encode(), ctypes.byref(r), err, 512)
@@ -74,10 +85,8 @@ def test_records_match_python_restatement(lib, name, w, h, ap, fl):
 
 
 @pytest.mark.parametrize("name", MESH_SCENES)
-def test_mesh_records_match_fixtures(lib, name):
-    if not os.path.exists(os.path.join(ASSETS, "teapot.obj")):
-        pytest.skip("OBJ assets not present (reference checkout)")
-    objs, tris, grps, cam = _build(lib, name, 64, 48)
+def test_mesh_records_match_fixtures(lib, assets, name):
+    objs, tris, grps, cam = _build(lib, name, 64, 48, assets=assets)
     po, pt, pg, pc = scene_inputs(name, 64, 48)  # fixture records (shared meshes resolved)
     assert objs.tobytes() == po.tobytes()
     assert tris.tobytes() == pt.tobytes()
@@ -85,11 +94,12 @@ def test_mesh_records_match_fixtures(lib, name):
     assert cam == np.asarray(pc).reshape(1).tobytes()
 
 
-def test_glass_scene_needs_its_missing_mesh(lib):
+def test_glass_scene_needs_its_missing_mesh(lib, assets, monkeypatch):
     """GlassScene reads assets/glass.obj, which the reference does not ship: both
     restatements fail loudly, as the Go os.ReadFile panic does."""
+    monkeypatch.setattr(scenes, "ASSETS", assets)  # the Python restatement reads the same fixture directory
     with pytest.raises(RuntimeError, match="glass.obj"):
-        _build(lib, "glass", 16, 12)
+        _build(lib, "glass", 16, 12, assets=assets)
     with pytest.raises(FileNotFoundError):
         scenes.SCENES["glass"](16, 12)
 

@@ -4,7 +4,7 @@
 #   tests                      full `pytest -m gpu` of the product build
 #   parity:<lib>               tests/test_gpu_parity.py against build/exp/libptmi_<lib>.so
 #   ab:<spp>:<cfgs>:<variants> tools/diag_ab.sh (cfgs / variants comma-separated)
-#   bench                      the default bench command (the driver's)
+#   bench                      the default bench command with every secondary measurement (bench.py --full)
 #   prof:<cfg>                 rocprofv3 --kernel-trace --stats of bench.py --config <cfg> --extra none
 #   profx:<name>:<lib>:<args>  the same for build/<lib>.so and bench args (comma-separated), e.g. the split form
 #   pmc:<cfg>:<counters>       one rocprofv3 --pmc pass (counters comma-separated) of the same
@@ -30,7 +30,7 @@ for step in "$@"; do
     ab)
       bash tools/diag_ab.sh $OUT/ab $a "${b//,/ }" "${c//,/ }" || exit 1 ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+      timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
       python3 -c "import json;d=json.load(open('$OUT/bench.json'));print('value',d['value'],'ms',d['ms_per_step'],'frac',d['roofline']['frac'],{k:v['ms_per_step'] for k,v in d.get('extra_configs',{}).items()})" ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$a -o run -- python3 bench.py --config $a --steps 3 \

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A round's final evidence on the GPU box (repo root):  bash tools/profile_final.sh <outdir>
-# 1. rocprofv3 --kernel-trace --stats of the driver's default bench command (C2 headline,
+# 1. rocprofv3 --kernel-trace --stats of the default bench command with --full (C2 headline,
 #    then the C3/C4/C5 extras and the statistical-RNG C2 frames in the same process)
 # 2. kernel-trace stats of one full 2048-spp frame of each of C2..C5 on its own
 # 3. FETCH_SIZE / WRITE_SIZE (separate --pmc passes, no tracing domains) for C2, C4, C5
@@ -18,7 +18,7 @@ mkdir -p $OUT
 ONE="--steps 1 --warmup 1 --no-cpu-baseline --no-trace-call --extra none"
 if has trace; then
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -o run -- \
-    python3 bench.py --steps 5 --warmup 2 > $OUT/bench_default.json 2> $OUT/bench_default.err
+    python3 bench.py --full --steps 5 --warmup 2 > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "default done"
 for c in c2 c3 c4 c5; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$c -o run -- \
