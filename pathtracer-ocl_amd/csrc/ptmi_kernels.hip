@@ -48,7 +48,8 @@
 // [42] other-normal block [43] emission block [44] shading past the miss test [45] prims
 // [46] active lanes summed over the iterations that run prims; [47] / [48] / [49] floor-ceiling plane
 // pairs / other plane pairs / single planes [50] / [51] / [52] first sphere pair / later pairs / single
-// [53] iterations of the loop over spheres with other matrices.
+// [53] iterations of the loop over spheres with other matrices [54] emission-only last records
+// (bounce_tail, lockstep loop; there [32] counts samples and [44] the full shading blocks).
 __device__ unsigned long long ptmi_stats[80];
 // Per-wave accumulators (one writer per wave: the first active lane), flushed to
 // ptmi_stats with one atomic per counter when the wave leaves its loop, so clock
@@ -124,6 +125,14 @@ __shared__ unsigned long long ptmi_wstat[1][64];
 #define PTMI_R6_NPAIR 0  // the two draws of a noise3D pair evaluated together (ptmi_sinf.h noise_sinf2):
                          // 1 both sites, 2 camera only, 3 hemisphere only.  Measured slower, C2 +0.6 / +0.3 /
                          // +0.5 % (its two interleaved chains hold more registers at the peak)
+#endif
+
+// The lockstep item loop of the all-diffuse kernels without meshes (trace_kernel, kLockstepOf): a wave
+// runs its 64 pixels' sample n together, so the bounce index is wave-uniform and a path's last bounce
+// runs the emission step alone (DESIGN.md s2 "a path's dead tail").  0: the regeneration loop with the
+// camera buffer and the full shading on every bounce, for A/B builds (tools/build_variant.sh).  Same images.
+#ifndef PTMI_LOCKSTEP
+#define PTMI_LOCKSTEP 1
 #endif
 
 namespace ptmi {
@@ -1938,12 +1947,55 @@ __device__ __noinline__ d4 plane_normal_map(const DevTexArray T, const DevObject
 // kMaskLds: the path's mask (throughput) lives in LDS at msk[0, kBlock, 2 kBlock] instead of
 // P.mr/mg/mb (the mesh kernels, where the 4-wave register budget otherwise spills it with a
 // scratch load and store per bounce).
-template <int FL, bool kAccLds = false, bool kMaskLds = false>
+// Which instantiations take the lockstep item loop (PTMI_LOCKSTEP): all-diffuse affine scenes without
+// meshes or textures.  There every hit is an effective bounce (no reflection or refraction), so the
+// bounce index b is also effectiveBounces, and a path has at most kMaxEffectiveBounces records.
+template <int FL>
+constexpr bool kLockstepOf = PTMI_LOCKSTEP != 0 && !(FL & (F_GROUPS | F_MATERIALS | F_PROJ | F_TEX));
+
+// A path's last bounce record (lockstep loop): the path ends at this hit -- the object is emissive
+// (tracer.cl:1107) or effectiveBounces reaches its bound (tracer.cl:884) -- and the reduction
+// (tracer.cl:1119-1176) reads only the record's emission, and its colour when it is record 0 and
+// emissive.  So bounce_shade's emission step runs alone, in its arithmetic and order; the record's
+// position, normal and cosine, the mask update and the next ray are never read.
+__device__ __forceinline__ void bounce_tail(const DevScene& S, const PathState& P, const Hit& h, uint32_t b,
+                                            double* acm) {
+    if (h.pk < 0) return;
+    PTMI_WADD(54, 1ull);
+    const DevObject& ob = S.objs[h.pk & 0xFFFF];
+    const double er = ob.emission[0], eg = ob.emission[1], eb = ob.emission[2];
+    // accumColor += mask * emission (see bounce_shade: skipped when every product is +-0)
+    const double tr = P.mr * er, tg = P.mg * eg, tb = P.mb * eb;
+    if (!(tr == 0.0 && tg == 0.0 && tb == 0.0)) {
+        acm[0 * kBlock] = acm[0 * kBlock] + tr;
+        acm[1 * kBlock] = acm[1 * kBlock] + tg;
+        acm[2 * kBlock] = acm[2 * kBlock] + tb;
+    }
+    if (er > 0.0) {
+        PTMI_WADD(43, 1ull);
+        if (b == 0) {  // the reduction's first record (tracer.cl:1160)
+            acm[0 * kBlock] = ob.color[0];
+            acm[1 * kBlock] = ob.color[1];
+            acm[2 * kBlock] = ob.color[2];
+        }
+    }
+}
+
+// kTail (the lockstep loop only, kLockstepOf): a hit on an emissive object ends the path, so it takes
+// bounce_tail and nothing else.
+template <int FL, bool kAccLds = false, bool kMaskLds = false, bool kTail = false>
 __device__ __forceinline__ bool bounce_shade(const DevScene& S, PathState& P, const Hit& h, float fgi, uint32_t n,
                                              double* acm = nullptr, double* msk = nullptr) {
     constexpr bool A = !(FL & F_PROJ);
     constexpr bool kX = (FL & F_XRNG) != 0;
     if (h.pk < 0) return true;  // a miss repeats identically until b == 10 in the reference
+    if constexpr (kTail) {
+        static_assert(kLockstepOf<FL> && kAccLds && !kMaskLds, "the lockstep loop's form");
+        if (S.objs[h.pk & 0xFFFF].emission[0] > 0.0) {
+            bounce_tail(S, P, h, P.b, acm);
+            return true;
+        }
+    }
     PTMI_WADD(44, 1ull);
     const DevObject& ob = S.objs[h.pk & 0xFFFF];
     const int type = ob.type;
@@ -2138,8 +2190,13 @@ __device__ __forceinline__ bool bounce_shade(const DevScene& S, PathState& P, co
                       // (80 VGPRs, 64 B/lane of spilled loop invariants) gain another 2-2.6 % (C2 171.5 ->
                       // 167.9, C3 179.5 -> 174.9 ms); 7 waves (72 VGPRs, 96 B/lane) lose 10 %
 #endif
+#ifndef PTMI_WAVES_LOCKSTEP_DOF
+#define PTMI_WAVES_LOCKSTEP_DOF 6  // ... the lockstep loop with DoF: at 72 VGPRs it spills 48 B/lane of per-sample
+                                   // values; same box, 2048 spp: C3 130.1 ms at 7 waves, 124.7 at 6 (C2, no DoF,
+                                   // prefers 7: 120.0 against 121.1 ms; profiles/lockstep/SUMMARY.md)
+#endif
 #ifndef PTMI_WAVES_MATERIALS
-#define PTMI_WAVES_MATERIALS 5  // ... with reflective / refractive materials: ~95-101 VGPRs since round 3 (LDS colour
+#define PTMI_WAVES_MATERIALS 5 // ... with reflective / refractive materials: ~95-101 VGPRs since round 3 (LDS colour
                                 // sums and accumColor), 0-32 B/lane of spill at 5; 256 spp: transparency 56.7 -> 53.5,
                                 // reflection 28.0 -> 24.9, default 37.4 -> 35.6 ms against 3 waves (4: within 1 %)
 #endif
@@ -2844,9 +2901,117 @@ __device__ __forceinline__ uint32_t take_item(uint32_t* __restrict__ ctr) {
     return blockIdx.x;
 #endif
 }
+// Lockstep item loop (kLockstepOf: the all-diffuse kernels without meshes).  The wave runs sample n of
+// its 64 pixels together: camera rays straight into registers, then at most kMaxEffectiveBounces
+// bounces with a wave-uniform bounce index b.  A lane whose path has ended (a miss, the light, a NaN
+// DoF ray) idles until the next sample; lanes outside the image get no samples.  On the last possible
+// bounce the wave runs bounce_tail alone: the shading block -- hit position, normal, two noise draws,
+// hemisphere direction, cosine, mask products -- is not executed there at all, which a per-lane test
+// inside the regeneration loop could not achieve (its lanes sit at all four bounce indices).  Every
+// path keeps its fgi, fgi2, n, b and arithmetic, a path ends exactly where bounce_shade's return value
+// ends it, and a pixel's `colors +=` stays in sample order: the frames are bit-identical to the
+// regeneration loop's.  No camera buffer, no refill thresholds.
+template <int FL>
+__device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
+                                               const double* __restrict__ seeds, const double* __restrict__ sunf,
+                                               double* __restrict__ sums, double* __restrict__ part) {
+    static_assert(kLockstepOf<FL>, "all-diffuse affine kernels without meshes");
+    static_assert(kMaxEffectiveBounces <= kMaxBounces, "a path ends by its effective bounces");
+    constexpr bool A = true;
+    constexpr bool kDof = (FL & F_DOF) != 0;
+    const int tid = threadIdx.x, lane = tid & 63;
+#if PTMI_STATS
+    ptmi_wstat[0][lane] = 0;
+#endif
+    const Item it = work_item(S0, WP, blockIdx.x, lane);
+    if (!it.ok) return;
+    const int px = it.px, py = it.py;
+    // fgi / fgi2 (tracer.cl:839-841): double division rounded to float.
+    const double seed = it.inside ? seeds[it.i] : 0.0;
+    const float fgi = (float)(seed / (double)S0.n_list);
+    const float fgi2 = (float)(seed / (double)samples);
+    const XSeed seed_bits = xseed_of((uint64_t)__double_as_longlong(seed));  // statistical mode
+    const bool inside = it.inside;
+    // The item's sample range is the same for every lane of the wave.
+    const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)it.c0);
+    const uint32_t c1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)it.c1);
+    // colors (tracer.cl:1179) and the current path's accumColor: one LDS slot per lane each, as in
+    // trace_kernel's regeneration loop (volatile: really in LDS, not promoted to VGPRs).
+    __shared__ double acc_lds[3 * kBlock];
+#if PTMI_R6_VACC
+    volatile __attribute__((address_space(3))) double* acc =
+        (volatile __attribute__((address_space(3))) double*)(acc_lds + tid);
+#else
+    double* acc = acc_lds + tid;
+#endif
+    acc[0 * kBlock] = 0.0;
+    acc[1 * kBlock] = 0.0;
+    acc[2 * kBlock] = 0.0;
+    __shared__ double acm_lds[3 * kBlock];
+    double* acm = acm_lds + tid;
+    PathState P;
+    PTMI_TSTAMP(t_loop);
+    for (uint32_t n = c0; n < c1; n++) {
+        PTMI_TSTAMP(t_a);
+        bool alive = inside;
+        if (alive) {
+            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
+            const DevCamera& cam = camera_ptr<(PTMI_CAM_RELOAD & 1) != 0>(S);
+            PTMI_WADD(32, 1ull);
+            d4 ro, rd;
+            float rx, ry;
+            camera_offsets<FL>(fgi, fgi2, seed_bits, n, rx, ry);
+            ray_for_pixel<kDof, A>(cam, sunf, (unsigned)px, (unsigned)py, rx, ry, (int)n, ro, rd);
+            start_path<A, kDof>(P, ro, rd);
+            acm[0 * kBlock] = 0.0;
+            acm[1 * kBlock] = 0.0;
+            acm[2 * kBlock] = 0.0;
+            if constexpr ((FL & F_XRNG) != 0) P.rng = xseed(seed_bits, n);
+        }
+        PTMI_TADD(12, t_a);
+        for (uint32_t b = 0; __any(alive); b++) {
+            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
+            if (alive) {
+                PTMI_TSTAMP(t_b);
+                PTMI_WADD(45, 1ull);
+                PTMI_WADD(46, (unsigned long long)__popcll(__ballot(1)));
+                Hit h;
+                if (P.dead) h.pk = -1;
+                else h = find_closest_prims<FL>(S, P.ro, P.rd);
+                PTMI_TADD(13, t_b);
+                PTMI_TSTAMP(t_d);
+                // b is the path's bounce index and its effectiveBounces, for every lane alike.
+                P.b = P.effective = b;
+                bool ended = true;
+                if (b + 1 >= kMaxBounces || b + 1 >= kMaxEffectiveBounces)  // (wave-uniform) the last record
+                    bounce_tail(S, P, h, b, acm);
+                else
+                    ended = bounce_shade<FL, true, false, true>(S, P, h, fgi, n, acm);
+                if (ended) {
+                    acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
+                    acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
+                    acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+                    alive = false;
+                }
+                PTMI_TADD(15, t_d);
+            }
+            PTMI_WADD(10, 1ull);
+        }
+    }
+    PTMI_TADD(16, t_loop);
+#if PTMI_STATS
+    if (PTMI_FIRST_ACTIVE())
+        for (int k = 0; k < 64; k++)
+            if (ptmi_wstat[0][k]) atomicAdd(&ptmi_stats[k], ptmi_wstat[0][k]);
+#endif
+    store_sums<true>(work_item(S0, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
+                     acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
+}
+
 template <int FL>
 __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                                                   : (FL & F_MATERIALS) ? PTMI_WAVES_MATERIALS
+                                                  : (kLockstepOf<FL> && (FL & F_DOF)) ? PTMI_WAVES_LOCKSTEP_DOF
                                                                        : PTMI_WAVES) void trace_kernel(DevScene S, uint32_t samples, WorkPlan WP,
                                                     const double* __restrict__ seeds, const double* __restrict__ sunf,
                                                     double* __restrict__ sums, double* __restrict__ part,
@@ -2874,6 +3039,14 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
 #endif
     } else if constexpr (kPoolFlatOf<FL>) {
         trace_flat_pool<FL>(S, samples, WP, seeds, sunf, sums, part);
+    } else if constexpr (kLockstepOf<FL>) {
+        trace_lockstep<FL>(S, samples, WP, seeds, sunf, sums, part);
+#if PTMI_TIMELINE
+        if (threadIdx.x == 0 && blockIdx.x < ptmi_tl_max) {
+            ptmi_tl[2 * blockIdx.x] = tl0;
+            ptmi_tl[2 * blockIdx.x + 1] = wall_clock64();
+        }
+#endif
     } else {
         constexpr bool A = !(FL & F_PROJ);
         const int tid = threadIdx.x, lane = tid & 63;

@@ -121,6 +121,8 @@ def subphase(chain, fr, src_lines, fp):
         if in_fn("hemi_sqrt"):
             return "hemisphere", "sqrt_fallback"
         return "hemisphere", "table_basis"
+    if in_fn("bounce_tail"):  # the lockstep loop's emission-only last record (also inlined into bounce_shade)
+        return "shading", "tail"
     if in_fn("bounce_shade"):
         a, b = fr["bounce_shade"]
         for f, ln in chain:
@@ -302,7 +304,9 @@ def executions(v):
          ("spheres", "roots_inplace"): v[34], ("hemisphere", "table_basis"): v[44],
          ("hemisphere", "sincos_fallback"): v[35], ("hemisphere", "sqrt_fallback"): v[36],
          ("shading", "common"): v[44], ("shading", "plane_normal"): v[41],
-         ("shading", "other_normal"): v[42], ("shading", "emission"): v[43]}
+         ("shading", "other_normal"): v[42], ("shading", "emission"): v[43],
+         # lockstep loop: [32] counts samples (the outer loop's camera block), [54] the emission-only records
+         ("shading", "tail"): v[54]}
     for site, n in (("camera", cam_draws), ("shading", shade_draws)):
         # the two draws of a site run back to back: a site's code holds both copies, so its
         # executions are pairs (n / 2)
