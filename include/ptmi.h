@@ -186,6 +186,47 @@ int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, ui
                       uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev,
                       double* sums_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len);
 
+/*
+ * ptmi_scene_render, also writing sq_dev[W*H]: for owned pixels the sum over the
+ * range's paths of (r*r + g*g) + b*b of the path's colour (separately rounded
+ * FP64, added where and in the order the colour is added), 0 for the others.
+ * sums_dev is bit-identical to ptmi_scene_render's for the same arguments: the
+ * work plan, chunks and tile ownership are the same.  A NaN path colour makes
+ * the pixel's entry NaN, as it makes its sums NaN.  Timing and the RNG mode
+ * apply as to ptmi_scene_render.  PTMI_ERR_ARG when a work item of a pooled
+ * (affine mesh, parity mode) scene would hold 2^26 samples or more: pass more
+ * chunks.
+ */
+int ptmi_scene_render_moments(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
+                              uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev,
+                              double* sums_dev, double* sq_dev, uint32_t chunks, void* hip_stream,
+                              char* err, size_t err_len);
+
+/*
+ * The standard error of each pixel's mean from frame sums (r, g, b, n per pixel)
+ * and second moments.  Per pixel i, n = sums_dev[4i+3]:
+ *   n == 0: se = 0 (not owned);  n == 1: se = +inf;  otherwise
+ *   mean_c = sum_c / n
+ *   d   = sq[i] / n - ((mean_r*mean_r + mean_g*mean_g) + mean_b*mean_b)
+ *   var = max(d, 0) * (n / (n - 1)),   se = sqrt(var / n)
+ * (the root of the three channels' summed variances of the mean).
+ *   se_dev[W*H]        se per pixel (may be NULL)
+ *   tile_err_dev[t]    per 8x8 tile, raster order: sqrt(mean of se^2 over the
+ *                      tile's in-image pixels with n >= 2), 0 when none (may be NULL)
+ *   stats_dev[0..4)    over all pixels with n >= 2: sqrt(mean se^2); the largest
+ *                      finite se; the mean of (mean_r + mean_g + mean_b) / 3;
+ *                      their number
+ * Both reductions run in a fixed order: equal inputs give equal bits.
+ */
+int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width, uint32_t height,
+                   double* se_dev, double* tile_err_dev, double* stats_dev, void* hip_stream,
+                   char* err, size_t err_len);
+
+/* dst_dev[k] += src_dev[k] over n doubles, on the caller's stream: batches of sums
+ * (A included, so the sample counts add) and of second moments. */
+int ptmi_accumulate(double* dst_dev, const double* src_dev, size_t n, void* hip_stream, char* err,
+                    size_t err_len);
+
 /* out_dev[i] = sums_dev[i] * (1.0 / samples) for RGB, 1.0 for A (tracer.cl:837,1184-1187). */
 int ptmi_finalize(const double* sums_dev, double* out_dev, uint32_t n_pixels, uint32_t samples,
                   void* hip_stream, char* err, size_t err_len);

@@ -33,11 +33,14 @@
 
 namespace ptmi {
 hipError_t launch_trace(const DevScene& S, int flags, uint32_t samples, const WorkPlan& WP, const double* seeds,
-                        const double* sunf, double* sums, double* part, uint32_t* item_ctr,
+                        const double* sunf, double* sums, double* part, uint32_t* item_ctr, double* sq,
                         hipStream_t st);
 hipError_t launch_sunflower(double* out, uint32_t samples, hipStream_t st);
-hipError_t launch_reduce(const double* part, double* sums, const WorkPlan& WP, int W, int H, bool planes,
+hipError_t launch_reduce(const double* part, double* sums, const WorkPlan& WP, int W, int H, bool planes, double* sq,
                          hipStream_t st);
+hipError_t launch_error_map(const double* sums, const double* sq, uint32_t W, uint32_t H, double* se, double* tile_err,
+                            double* tile_part, double* stats, hipStream_t st);
+hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream_t st);
 hipError_t launch_finalize(const double* sums, double* out, uint32_t npix, uint32_t samples, hipStream_t st);
 hipError_t launch_seeds(double* seeds, uint32_t n, uint64_t stream, hipStream_t st);
 hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st);
@@ -926,9 +929,13 @@ static bool diagonal_tiles(const ptmi_scene* s, uint32_t tile_stride) {
     return tile_stride > 1 && tile_list_supported(kflags0) && tiles_x % tile_stride == 0;
 }
 
-int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
-                      uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev, double* sums_dev,
-                      uint32_t chunks, void* hip_stream, char* err, size_t err_len) {
+}  // extern "C"
+
+// ptmi_scene_render (sq_dev == nullptr) and ptmi_scene_render_moments (sq_dev: W*H second moments):
+// one plan for both, so the moment render's colour sums are the plain render's bit for bit.
+static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
+                        uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev, double* sums_dev,
+                        double* sq_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len) {
     if (!s || !seeds_dev || !sums_dev || samples == 0 || sample_begin > sample_end || sample_end > samples ||
         tile_stride == 0 || tile_offset >= tile_stride) {
         set_err(err, err_len, "bad render arguments (samples %u range [%u,%u) tiles %u/%u)", samples, sample_begin,
@@ -1078,6 +1085,21 @@ int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, ui
         }
         wp.tiles = s->tlist_dev;
     }
+    if (sq_dev) {
+#if PTMI_STUDY
+        if (split) {
+            set_err(err, err_len, "the split execution form has no moment variant");
+            return PTMI_ERR_UNSUPPORTED;
+        }
+#endif
+        // The path pool numbers an item's paths 64 x its samples in 32 bits (trace_groups_pool's
+        // `total`): with or without a tile list, an item of 2^26 samples or more would wrap.
+        if (pooled && (uint64_t)std::max(wp.chunk_len, wp.tail_len) >= (1ull << 26) && range > 0) {
+            set_err(err, err_len, "moment render: a pooled work item of %u samples (>= 2^26); use more chunks",
+                    std::max(wp.chunk_len, wp.tail_len));
+            return PTMI_ERR_ARG;
+        }
+    }
     const bool mesh_plan = (s->flags & 1) != 0;  // F_GROUPS
     if (!split && s->tile_order && owned_tiles > 0 && mesh_plan) {
         // Mesh scenes: the dispatch order of the work items -- whole tiles among themselves,
@@ -1148,8 +1170,10 @@ int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, ui
         }
     }
     if (tile_stride > 1) HIP_TRY(hipMemsetAsync(sums_dev, 0, (size_t)npix * 4 * sizeof(double), st));  // un-owned tiles
+    if (tile_stride > 1 && sq_dev) HIP_TRY(hipMemsetAsync(sq_dev, 0, (size_t)npix * sizeof(double), st));
     const bool planes = (s->flags & 1) == 0 || (PTMI_MESH_PLANES && !split);  // partial layout (ptmi_kernels.hip store_sums)
-    const size_t need = (size_t)wp.n_tail * 64 * chunks * (planes ? 3 : 4) * sizeof(double);
+    // (moment renders: one more plane of partials, ptmi_kernels.hip store_mom)
+    const size_t need = (size_t)wp.n_tail * 64 * chunks * ((planes ? 3 : 4) + (sq_dev ? 1 : 0)) * sizeof(double);
     if (need > s->partial_bytes) {
         if (s->partial) {
             HIP_TRY(hipStreamSynchronize(st));
@@ -1172,7 +1196,8 @@ int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, ui
     } else
 #endif
     {
-        HIP_TRY(launch_trace(s->dev, kflags, samples, wp, seeds_dev, s->sunf, sums_dev, s->partial, s->item_ctr, st));
+        HIP_TRY(launch_trace(s->dev, kflags | (sq_dev ? 512 : 0) /* F_MOM */, samples, wp, seeds_dev, s->sunf, sums_dev,
+                             s->partial, s->item_ctr, sq_dev, st));
     }
     if (ev1) {
         HIP_TRY(hipEventRecord(ev1, st));
@@ -1182,7 +1207,53 @@ int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, ui
     // after the timed launch: the next launch's order from this one's item durations
     if (wp.cost) HIP_TRY(launch_tile_order(wp.cost, wp.n_whole, wp.n_tail, tile_stride, tile_offset, s->order_dev, st));
 #endif
-    HIP_TRY(launch_reduce(s->partial, sums_dev, wp, (int)W, (int)H, planes, st));
+    HIP_TRY(launch_reduce(s->partial, sums_dev, wp, (int)W, (int)H, planes, sq_dev, st));
+    return PTMI_OK;
+}
+
+extern "C" {
+
+int ptmi_scene_render(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
+                      uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev, double* sums_dev,
+                      uint32_t chunks, void* hip_stream, char* err, size_t err_len) {
+    return render_frame(s, samples, sample_begin, sample_end, tile_stride, tile_offset, seeds_dev, sums_dev, nullptr,
+                        chunks, hip_stream, err, err_len);
+}
+
+int ptmi_scene_render_moments(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
+                              uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev, double* sums_dev,
+                              double* sq_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len) {
+    if (!sq_dev) {
+        set_err(err, err_len, "ptmi_scene_render_moments: sq_dev == NULL");
+        return PTMI_ERR_ARG;
+    }
+    return render_frame(s, samples, sample_begin, sample_end, tile_stride, tile_offset, seeds_dev, sums_dev, sq_dev,
+                        chunks, hip_stream, err, err_len);
+}
+
+int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width, uint32_t height, double* se_dev,
+                   double* tile_err_dev, double* stats_dev, void* hip_stream, char* err, size_t err_len) {
+    if (!sums_dev || !sq_dev || !stats_dev || width == 0 || height == 0) {
+        set_err(err, err_len, "bad error-map arguments");
+        return PTMI_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    // The tiles' partial summaries between the two kernels: stream-ordered scratch.
+    const size_t tiles = (size_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
+    double* tile_part = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&tile_part, tiles * 4 * sizeof(double), st));
+    const hipError_t e = launch_error_map(sums_dev, sq_dev, width, height, se_dev, tile_err_dev, tile_part, stats_dev, st);
+    HIP_TRY(hipFreeAsync(tile_part, st));
+    HIP_TRY(e);
+    return PTMI_OK;
+}
+
+int ptmi_accumulate(double* dst_dev, const double* src_dev, size_t n, void* hip_stream, char* err, size_t err_len) {
+    if (!dst_dev || !src_dev) {
+        set_err(err, err_len, "bad accumulate arguments");
+        return PTMI_ERR_ARG;
+    }
+    HIP_TRY(launch_accumulate(dst_dev, src_dev, n, (hipStream_t)hip_stream));
     return PTMI_OK;
 }
 

@@ -560,6 +560,8 @@ enum : int {
     F_TLIST = 128,    // tile-split launch with an owned-tile list (WorkPlan::tiles): affine mesh kernels only
     F_XRNG = 64,      // opt-in statistical mode (ptmi_scene_set_rng): xoshiro128** instead of noise3D,
                       // affine instantiations only; never the parity path
+    F_MOM = 512,      // moment variant (ptmi_scene_render_moments): each finished path also adds
+                      // (r*r + g*g) + b*b of its accumColor into the pixel's second moment (mom_add)
     F_WIDE = 256      // affine mesh scene whose child codes need 31 bits (>= 2^15 Node4s or triangles):
                       // the affine kernel with a 32-bit LDS traversal stack (one F_ALL | F_WIDE
                       // instantiation, +- F_XRNG; ADVICE r5: such scenes had been sent to F_PROJ)
@@ -2258,6 +2260,25 @@ __device__ __forceinline__ Item work_item(const DevScene& S, const WorkPlan& WP,
     return it;
 }
 
+// Moment variant (F_MOM): the finished path's q = (r*r + g*g) + b*b, separately rounded, added to the
+// pixel's second moment right after its three `colors +=` adds (same place, same order).  A NaN
+// colour makes q NaN as it makes the sums NaN; the DoF sample-0 NaN ray ends with accumColor 0 and
+// adds 0.
+__device__ __forceinline__ double mom_q(double r, double g, double b) { return (r * r + g * g) + b * b; }
+// Where an item's second moment goes: a whole-tile item's into sq[pixel]; a chunk item's into one
+// more plane of the partial buffer, after the 3 colour planes (kPlanes) or the 4-double records.
+template <bool kPlanes>
+__device__ __forceinline__ void store_mom(const Item& it, const WorkPlan& WP, double* __restrict__ sq,
+                                          double* __restrict__ part, double m2) {
+    if (!it.inside) return;
+    if (it.whole) {
+        __builtin_nontemporal_store(m2, sq + it.oslot);
+        return;
+    }
+    const size_t plane = (size_t)WP.nchunks * WP.n_tail * 64;
+    __builtin_nontemporal_store(m2, part + (kPlanes ? 3 : 4) * plane + it.oslot);
+}
+
 // A whole-tile item writes its pixel's (r, g, b, samples) into the frame sums.  A chunk
 // item: kPlanes, its r, g, b into plane k of the partial buffer at
 // k * (nchunks * n_tail * 64) + oslot, the sample counts re-derived by reduce_chunks_kernel
@@ -2361,9 +2382,11 @@ constexpr bool kPoolOf = PTMI_POOL != 0 && (FL & F_GROUPS) != 0 && !(FL & (F_PRO
 template <int FL>
 __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
                                              const double* __restrict__ seeds, const double* __restrict__ sunf,
-                                             double* __restrict__ sums, double* __restrict__ part, uint32_t item) {
+                                             double* __restrict__ sums, double* __restrict__ part, uint32_t item,
+                                             double* __restrict__ sq) {
     constexpr bool A = !(FL & F_PROJ);
     constexpr bool kDof = (FL & F_DOF) != 0;
+    constexpr bool kMom = (FL & F_MOM) != 0;
     constexpr int kCamComp = (kDof || !A) ? (A ? 6 : 8) : 3;  // see trace_kernel
     const DevScene& S = S0;
     // Per-lane BVH traversal stacks, lane-interleaved (entry k of lane t at
@@ -2409,6 +2432,11 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
     acc[0 * kBlock] = 0.0;
     acc[1 * kBlock] = 0.0;
     acc[2 * kBlock] = 0.0;
+    // (F_MOM) the pixel's second moment, one more LDS slot per lane beside the colour sums
+    __shared__ double m2_lds[kMom ? kBlock : 1];
+    volatile __attribute__((address_space(3))) double* m2 =
+        (volatile __attribute__((address_space(3))) double*)(m2_lds + (kMom ? tid : 0));
+    if constexpr (kMom) m2[0] = 0.0;
     double* acm = kAcm ? acm_lds + tid : nullptr;
     double* msk = kMsk ? msk_lds + tid : nullptr;
     uint32_t n_gen = it.c0;
@@ -2540,10 +2568,12 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
                 acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
                 acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
                 acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+                if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
             } else {
                 acc[0 * kBlock] = acc[0 * kBlock] + P.ar;
                 acc[1 * kBlock] = acc[1 * kBlock] + P.ag;
                 acc[2 * kBlock] = acc[2 * kBlock] + P.ab;
+                if constexpr (kMom) m2[0] = m2[0] + mom_q(P.ar, P.ag, P.ab);
             }
             active = false;
         }
@@ -2566,6 +2596,8 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
     // The work item is re-derived (a few integer operations) rather than kept live across
     // the loop: its fields would hold ~5 VGPRs through every walk phase.
     store_sums<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S, WP, item, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock], acc[2 * kBlock]);
+    if constexpr (kMom)
+        store_mom<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S, WP, item, lane), WP, sq, part, m2[0]);
 }
 
 // trace_groups with the path pool (kPoolOf above): the same loop, phases and walks; what
@@ -2574,9 +2606,10 @@ template <int FL>
 __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
                                                   const double* __restrict__ seeds, const double* __restrict__ sunf,
                                                   double* __restrict__ sums, double* __restrict__ part,
-                                                  uint32_t item) {
+                                                  uint32_t item, double* __restrict__ sq) {
     constexpr bool A = true;
     constexpr bool kDof = (FL & F_DOF) != 0;
+    constexpr bool kMom = (FL & F_MOM) != 0;
     constexpr int kCamComp = kDof ? 6 : 3;
     constexpr int kPoolStack = 21;  // ptmi_bvh.cpp kMaxNode4Depth * 3
     static_assert(kPoolStack <= kStack, "pool stack");
@@ -2589,6 +2622,9 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
     __shared__ double cam_lds[kCamComp * kBlock];
     __shared__ uint32_t ncur_lds[kBlock];  // the lane's current path j: pixel j & 63, sample c0 + (j >> 6)
     __shared__ float fgi_lds[kBlock];      // fgi of pixel t of the tile
+    // (F_MOM) second moment of pixel t of the tile: 512 B more per wave, which the 16-waves-per-CU
+    // LDS budget above does not have -- the moment instantiations run at 15 waves per CU
+    __shared__ double m2_lds[kMom ? kBlock : 1];
     const int tid = threadIdx.x, lane = tid & 63;
 #if PTMI_STATS
     ptmi_wstat[0][lane] = 0;
@@ -2600,6 +2636,7 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
     acc_lds[0 * kBlock + tid] = 0.0;
     acc_lds[1 * kBlock + tid] = 0.0;
     acc_lds[2 * kBlock + tid] = 0.0;
+    if constexpr (kMom) m2_lds[tid] = 0.0;
     // The lanes read each other's fgi and add into each other's sums from here on: a wave barrier
     // (one wave per workgroup; LDS serves a wave's operations in program order) keeps the compiler
     // from moving those accesses across the initialisation, and the one after the loop keeps the
@@ -2716,6 +2753,8 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
                 atomicAdd(&acc_lds[0 * kBlock + p], acm[0 * kBlock]);
                 atomicAdd(&acc_lds[1 * kBlock + p], acm[1 * kBlock]);
                 atomicAdd(&acc_lds[2 * kBlock + p], acm[2 * kBlock]);
+                // (F_MOM) after the pixel's three colour adds, whose order it leaves as it was
+                if constexpr (kMom) atomicAdd(&m2_lds[p], mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]));
                 active = false;
             }
         }
@@ -2723,6 +2762,8 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
     __builtin_amdgcn_wave_barrier();
     store_sums<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S0, WP, item, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
                                       acc_lds[1 * kBlock + tid], acc_lds[2 * kBlock + tid]);
+    if constexpr (kMom)
+        store_mom<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S0, WP, item, lane), WP, sq, part, m2_lds[tid]);
 }
 
 // The path pool for the kernels without meshes (PTMI_POOL_FLAT, affine non-DoF parity-mode scenes):
@@ -2742,10 +2783,13 @@ constexpr bool kPoolFlatOf = PTMI_POOL_FLAT != 0 && !(FL & (F_GROUPS | F_PROJ | 
 template <int FL>
 __device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
                                                 const double* __restrict__ seeds, const double* __restrict__ sunf,
-                                                double* __restrict__ sums, double* __restrict__ part) {
+                                                double* __restrict__ sums, double* __restrict__ part,
+                                                double* __restrict__ sq) {
     constexpr bool A = true;
     constexpr bool kDof = (FL & F_DOF) != 0;
+    constexpr bool kMom = (FL & F_MOM) != 0;
     constexpr int kCamComp = kDof ? 6 : 3;
+    __shared__ double m2_lds[kMom ? kBlock : 1];
     __shared__ double acc_lds[3 * kBlock];
     __shared__ double acm_lds[3 * kBlock];
     __shared__ double cam_lds[kCamComp * kBlock];
@@ -2764,6 +2808,7 @@ __device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t sam
     acc_lds[0 * kBlock + tid] = 0.0;
     acc_lds[1 * kBlock + tid] = 0.0;
     acc_lds[2 * kBlock + tid] = 0.0;
+    if constexpr (kMom) m2_lds[tid] = 0.0;
     __builtin_amdgcn_wave_barrier();  // (see trace_groups_pool)
     const int tx0 = __builtin_amdgcn_readfirstlane(it.px - (lane & 7));
     const int ty0 = __builtin_amdgcn_readfirstlane(it.py - (lane >> 3));
@@ -2844,6 +2889,7 @@ __device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t sam
                 atomicAdd(&acc_lds[0 * kBlock + p], acm[0 * kBlock]);
                 atomicAdd(&acc_lds[1 * kBlock + p], acm[1 * kBlock]);
                 atomicAdd(&acc_lds[2 * kBlock + p], acm[2 * kBlock]);
+                if constexpr (kMom) atomicAdd(&m2_lds[p], mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]));
                 active = false;
             }
         }
@@ -2851,6 +2897,7 @@ __device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t sam
     __builtin_amdgcn_wave_barrier();
     store_sums<true>(work_item(S0, WP, blockIdx.x, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
                      acc_lds[1 * kBlock + tid], acc_lds[2 * kBlock + tid]);
+    if constexpr (kMom) store_mom<true>(work_item(S0, WP, blockIdx.x, lane), WP, sq, part, m2_lds[tid]);
 }
 
 // Per-item duration onto its tile's cost accumulator (WorkPlan::cost, tile_order_kernel;
@@ -2914,8 +2961,10 @@ __device__ __forceinline__ uint32_t take_item(uint32_t* __restrict__ ctr) {
 template <int FL>
 __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
                                                const double* __restrict__ seeds, const double* __restrict__ sunf,
-                                               double* __restrict__ sums, double* __restrict__ part) {
+                                               double* __restrict__ sums, double* __restrict__ part,
+                                               double* __restrict__ sq) {
     static_assert(kLockstepOf<FL>, "all-diffuse affine kernels without meshes");
+    constexpr bool kMom = (FL & F_MOM) != 0;
     static_assert(kMaxEffectiveBounces <= kMaxBounces, "a path ends by its effective bounces");
     constexpr bool A = true;
     constexpr bool kDof = (FL & F_DOF) != 0;
@@ -2947,6 +2996,11 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
     acc[0 * kBlock] = 0.0;
     acc[1 * kBlock] = 0.0;
     acc[2 * kBlock] = 0.0;
+    // (F_MOM) the pixel's second moment, one more LDS slot per lane beside the colour sums
+    __shared__ double m2_lds[kMom ? kBlock : 1];
+    volatile __attribute__((address_space(3))) double* m2 =
+        (volatile __attribute__((address_space(3))) double*)(m2_lds + (kMom ? tid : 0));
+    if constexpr (kMom) m2[0] = 0.0;
     __shared__ double acm_lds[3 * kBlock];
     double* acm = acm_lds + tid;
     PathState P;
@@ -2991,6 +3045,8 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
                     acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
                     acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
                     acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+                    // (F_MOM) bounce_tail's and bounce_shade's paths end in the same add
+                    if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
                     alive = false;
                 }
                 PTMI_TADD(15, t_d);
@@ -3006,6 +3062,7 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
 #endif
     store_sums<true>(work_item(S0, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
                      acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
+    if constexpr (kMom) store_mom<true>(work_item(S0, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
 }
 
 template <int FL>
@@ -3015,7 +3072,10 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                                                                        : PTMI_WAVES) void trace_kernel(DevScene S, uint32_t samples, WorkPlan WP,
                                                     const double* __restrict__ seeds, const double* __restrict__ sunf,
                                                     double* __restrict__ sums, double* __restrict__ part,
-                                                    uint32_t* __restrict__ item_ctr) {
+                                                    uint32_t* __restrict__ item_ctr, double* __restrict__ sq) {
+    // sq: the second moments' frame (W*H doubles), read by the F_MOM instantiations only; the last
+    // argument, so that every other argument keeps its offset.
+    [[maybe_unused]] constexpr bool kMom = (FL & F_MOM) != 0;
 #if PTMI_TIMELINE
     const unsigned long long tl0 = wall_clock64();
 #endif
@@ -3025,9 +3085,9 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
         const unsigned long long c0 = WP.cost ? wall_clock64() : 0ull;
 #endif
         if constexpr (kPoolOf<FL>)
-            trace_groups_pool<FL>(S, samples, WP, seeds, sunf, sums, part, item);
+            trace_groups_pool<FL>(S, samples, WP, seeds, sunf, sums, part, item, sq);
         else
-            trace_groups<FL>(S, samples, WP, seeds, sunf, sums, part, item);
+            trace_groups<FL>(S, samples, WP, seeds, sunf, sums, part, item, sq);
 #if PTMI_TILE_COST
         item_cost_add(S, WP, item, c0);
 #endif
@@ -3038,9 +3098,9 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
         }
 #endif
     } else if constexpr (kPoolFlatOf<FL>) {
-        trace_flat_pool<FL>(S, samples, WP, seeds, sunf, sums, part);
+        trace_flat_pool<FL>(S, samples, WP, seeds, sunf, sums, part, sq);
     } else if constexpr (kLockstepOf<FL>) {
-        trace_lockstep<FL>(S, samples, WP, seeds, sunf, sums, part);
+        trace_lockstep<FL>(S, samples, WP, seeds, sunf, sums, part, sq);
 #if PTMI_TIMELINE
         if (threadIdx.x == 0 && blockIdx.x < ptmi_tl_max) {
             ptmi_tl[2 * blockIdx.x] = tl0;
@@ -3078,6 +3138,11 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
         acc[0 * kBlock] = 0.0;
         acc[1 * kBlock] = 0.0;
         acc[2 * kBlock] = 0.0;
+        // (F_MOM) the pixel's second moment, one more LDS slot per lane beside the colour sums
+        __shared__ double m2_lds[kMom ? kBlock : 1];
+        volatile __attribute__((address_space(3))) double* m2 =
+            (volatile __attribute__((address_space(3))) double*)(m2_lds + (kMom ? tid : 0));
+        if constexpr (kMom) m2[0] = 0.0;
         // accumColor of the lane's current path (bounce_shade kAccLds): 6 VGPRs fewer
         // through the bounce loop.
         __shared__ double acm_lds[3 * kBlock];
@@ -3170,6 +3235,7 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                     acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
                     acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
                     acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+                    if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
                     active = false;
                 }
                 PTMI_TADD(15, t_d);
@@ -3187,6 +3253,7 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                 acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
                 acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
                 acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+                if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
                 active = false;
             }
             PTMI_TADD(15, t_d);
@@ -3201,6 +3268,7 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
 #endif
         store_sums<true>(work_item(S, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
                    acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
+        if constexpr (kMom) store_mom<true>(work_item(S, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
 #if PTMI_TIMELINE
         if (threadIdx.x == 0 && blockIdx.x < ptmi_tl_max) {
             ptmi_tl[2 * blockIdx.x] = tl0;
@@ -3774,9 +3842,12 @@ hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st) {
 }
 
 // The tail tiles' chunk partials (WorkPlan) summed in chunk order (deterministic)
-// into the frame; one thread per tail-tile pixel.
+// into the frame; one thread per tail-tile pixel.  kMom (moment renders): the chunk items' second
+// moments (store_mom's plane) summed in chunk order likewise, into sq.
+template <bool kMom>
 __global__ __launch_bounds__(256) void reduce_chunks_kernel(const double* __restrict__ part, double* __restrict__ sums,
-                                                            WorkPlan WP, int W, int H, bool planes) {
+                                                            WorkPlan WP, int W, int H, bool planes,
+                                                            double* __restrict__ sq) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= WP.n_tail * 64) return;
     const uint32_t tt = j >> 6, lane = j & 63;
@@ -3786,8 +3857,12 @@ __global__ __launch_bounds__(256) void reduce_chunks_kernel(const double* __rest
     const int px = (int)(tile % (uint32_t)tiles_x) * kTile + (int)(lane & 7);
     const int py = (int)(tile / (uint32_t)tiles_x) * kTile + (int)(lane >> 3);
     if (px >= W || py >= H) return;
-    double r = 0.0, g = 0.0, b = 0.0, a = 0.0;
+    double r = 0.0, g = 0.0, b = 0.0, a = 0.0, m2 = 0.0;
     for (uint32_t c = 0; c < WP.nchunks; c++) {
+        if constexpr (kMom) {
+            const size_t plane = (size_t)WP.nchunks * WP.n_tail * 64;
+            m2 = m2 + part[(planes ? 3 : 4) * plane + (size_t)c * WP.n_tail * 64 + j];
+        }
         if (planes) {
             const size_t plane = (size_t)WP.nchunks * WP.n_tail * 64;
             const double* p = part + (size_t)c * WP.n_tail * 64 + j;  // store_sums' planes
@@ -3810,6 +3885,109 @@ __global__ __launch_bounds__(256) void reduce_chunks_kernel(const double* __rest
     o[1] = g;
     o[2] = b;
     o[3] = a;
+    if constexpr (kMom) sq[(size_t)py * W + px] = m2;
+}
+
+// ---- error map and accumulate (ptmi_error_map, ptmi_accumulate) ------------------------------
+// A pixel's standard error from its sums record (r, g, b, n) and second moment (ptmi/error.py
+// error_map_reference restates this operation for operation):
+//   n == 0: se = 0 (not owned);  n == 1: se = +inf;  else
+//   d = sq / n - ((mr*mr + mg*mg) + mb*mb),  var = max(d, 0) * (n / (n - 1)),  se2 = var / n,  se = sqrt(se2)
+// counted: n >= 2 (the pixels the summaries run over).  A NaN d stays NaN.
+struct PixelErr {
+    double se, se2, mean;
+    bool counted;
+};
+__device__ __forceinline__ PixelErr pixel_err(const double* __restrict__ sums, const double* __restrict__ sq,
+                                              size_t i) {
+    PixelErr e{0.0, 0.0, 0.0, false};
+    const double n = sums[4 * i + 3];
+    if (n == 0.0) return e;
+    if (n == 1.0) {
+        e.se = __builtin_inf();
+        return e;
+    }
+    const double mr = sums[4 * i + 0] / n, mg = sums[4 * i + 1] / n, mb = sums[4 * i + 2] / n;
+    const double d = sq[i] / n - ((mr * mr + mg * mg) + mb * mb);
+    const double var = (d < 0.0 ? 0.0 : d) * (n / (n - 1.0));
+    e.se2 = var / n;
+    e.se = sqrt(e.se2);
+    e.mean = ((mr + mg) + mb) / 3.0;
+    e.counted = true;
+    return e;
+}
+// A fixed-shape tree over the workgroup's kN slots (kN a power of two): the same inputs give the
+// same bits.  v[0] sums, v[1] maxima, v[2] sums, v[3] sums.
+template <int kN>
+__device__ __forceinline__ void err_tree(double (*v)[kN], int t) {
+    for (int s = kN / 2; s > 0; s >>= 1) {
+        __syncthreads();
+        if (t < s) {
+            v[0][t] = v[0][t] + v[0][t + s];
+            v[1][t] = v[1][t + s] > v[1][t] ? v[1][t + s] : v[1][t];
+            v[2][t] = v[2][t] + v[2][t + s];
+            v[3][t] = v[3][t] + v[3][t + s];
+        }
+    }
+    __syncthreads();
+}
+// One wave per 8x8 tile (kTile; raster order): se per pixel, the tile's rms se, and the tile's
+// (sum se2, max finite se, sum mean, count) into tile_part for error_stats.
+__global__ __launch_bounds__(64) void error_map(const double* __restrict__ sums, const double* __restrict__ sq, int W,
+                                                int H, double* __restrict__ se, double* __restrict__ tile_err,
+                                                double* __restrict__ tile_part) {
+    __shared__ double v[4][64];
+    const int t = threadIdx.x, tiles_x = (W + kTile - 1) / kTile;
+    const int px = (int)(blockIdx.x % (uint32_t)tiles_x) * kTile + (t & 7);
+    const int py = (int)(blockIdx.x / (uint32_t)tiles_x) * kTile + (t >> 3);
+    PixelErr e{0.0, 0.0, 0.0, false};
+    if (px < W && py < H) {
+        const size_t i = (size_t)py * W + px;
+        e = pixel_err(sums, sq, i);
+        if (se) se[i] = e.se;
+    }
+    v[0][t] = e.counted ? e.se2 : 0.0;
+    v[1][t] = (e.counted && e.se < __builtin_inf()) ? e.se : 0.0;  // (a NaN se compares false)
+    v[2][t] = e.counted ? e.mean : 0.0;
+    v[3][t] = e.counted ? 1.0 : 0.0;
+    err_tree<64>(v, t);
+    if (t == 0) {
+        if (tile_err) tile_err[blockIdx.x] = v[3][0] > 0.0 ? sqrt(v[0][0] / v[3][0]) : 0.0;
+        for (int k = 0; k < 4; k++) tile_part[4 * (size_t)blockIdx.x + k] = v[k][0];
+    }
+}
+// The frame's summaries from the tiles' (one workgroup): thread t folds tiles t, t + 256, ... in
+// that order, then the tree.  stats: rms se, max finite se, mean of the pixel means, pixel count.
+__global__ __launch_bounds__(256) void error_stats(const double* __restrict__ tile_part, uint32_t tiles,
+                                                   double* __restrict__ stats) {
+    __shared__ double v[4][256];
+    const int t = threadIdx.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (uint32_t k = (uint32_t)t; k < tiles; k += 256u) {
+        const double* p = tile_part + 4 * (size_t)k;
+        a0 = a0 + p[0];
+        a1 = p[1] > a1 ? p[1] : a1;
+        a2 = a2 + p[2];
+        a3 = a3 + p[3];
+    }
+    v[0][t] = a0;
+    v[1][t] = a1;
+    v[2][t] = a2;
+    v[3][t] = a3;
+    err_tree<256>(v, t);
+    if (t == 0) {
+        const double cnt = v[3][0];
+        stats[0] = cnt > 0.0 ? sqrt(v[0][0] / cnt) : 0.0;
+        stats[1] = v[1][0];
+        stats[2] = cnt > 0.0 ? v[2][0] / cnt : 0.0;
+        stats[3] = cnt;
+    }
+}
+// dst[k] += src[k] (frame sums, counts included, and second moments of successive batches).
+__global__ __launch_bounds__(256) void accumulate_sums(double* __restrict__ dst, const double* __restrict__ src,
+                                                       size_t n) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) dst[k] = dst[k] + src[k];
 }
 
 // colors * (1.0 / samples), alpha 1 (tracer.cl:837, 1184-1187).
@@ -3864,11 +4042,12 @@ int trace_tiles_per_block(int flags) { return 1; }
 // The instantiation a scene's flags launch: textured and non-affine scenes take the
 // generic ones; F_XRNG exists for the affine instantiations (ptmi_scene_set_rng).
 static int kernel_flags(int flags) {
-    if (flags & F_TEX) return F_ALL | F_PROJ | F_TEX;
-    if (flags & F_PROJ) return F_ALL | F_PROJ;
-    if (flags & F_WIDE) return F_ALL | F_WIDE | (flags & F_XRNG);
-    if ((flags & F_TLIST) && (flags & F_GROUPS) && !(flags & F_XRNG)) return flags & (F_ALL | F_TLIST);
-    return flags & (F_ALL | F_XRNG);
+    const int mom = flags & F_MOM;  // every instantiation has its moment variant
+    if (flags & F_TEX) return F_ALL | F_PROJ | F_TEX | mom;
+    if (flags & F_PROJ) return F_ALL | F_PROJ | mom;
+    if (flags & F_WIDE) return F_ALL | F_WIDE | (flags & F_XRNG) | mom;
+    if ((flags & F_TLIST) && (flags & F_GROUPS) && !(flags & F_XRNG)) return (flags & (F_ALL | F_TLIST)) | mom;
+    return (flags & (F_ALL | F_XRNG)) | mom;
 }
 
 int trace_kernel_flags(int flags) { return kernel_flags(flags); }
@@ -3880,8 +4059,9 @@ bool tile_list_supported(int flags) {
 
 const void* trace_kernel_symbol(int flags) {
     switch (kernel_flags(flags)) {
-#define K(f) \
-    case f: return reinterpret_cast<const void*>(&trace_kernel<f>);
+#define K(f)                                                          \
+    case f: return reinterpret_cast<const void*>(&trace_kernel<f>); \
+    case f | F_MOM: return reinterpret_cast<const void*>(&trace_kernel<f | F_MOM>);
         K(0) K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) K(10) K(11) K(12) K(13) K(14) K(15)
         K(F_ALL | F_PROJ) K(F_ALL | F_PROJ | F_TEX)
         K(64) K(65) K(66) K(67) K(68) K(69) K(70) K(71) K(72) K(73) K(74) K(75) K(76) K(77) K(78) K(79)
@@ -3893,16 +4073,22 @@ const void* trace_kernel_symbol(int flags) {
 }
 
 hipError_t launch_trace(const DevScene& S, int flags, uint32_t samples, const WorkPlan& WP, const double* seeds,
-                        const double* sunf, double* sums, double* part, uint32_t* item_ctr, hipStream_t st) {
+                        const double* sunf, double* sums, double* part, uint32_t* item_ctr, double* sq,
+                        hipStream_t st) {
     const uint32_t items = WP.n_whole + WP.n_tail * WP.nchunks;
     if (items == 0) return hipSuccess;
     flags = kernel_flags(flags);
+    if (((flags & F_MOM) != 0) != (sq != nullptr)) return hipErrorInvalidValue;
     const int threads = trace_block_threads(flags), wpb = trace_tiles_per_block(flags);
     const dim3 grid((items + wpb - 1) / wpb), block(threads);
     switch (flags) {
-#define K(f)                                                                                          \
-    case f:                                                                                           \
-        hipLaunchKernelGGL(trace_kernel<f>, grid, block, 0, st, S, samples, WP, seeds, sunf, sums, part, item_ctr); \
+#define K(f)                                                                                                        \
+    case f:                                                                                                         \
+        hipLaunchKernelGGL(trace_kernel<f>, grid, block, 0, st, S, samples, WP, seeds, sunf, sums, part, item_ctr, sq); \
+        break;                                                                                                      \
+    case f | F_MOM:                                                                                                 \
+        hipLaunchKernelGGL(trace_kernel<f | F_MOM>, grid, block, 0, st, S, samples, WP, seeds, sunf, sums, part,    \
+                           item_ctr, sq);                                                                           \
         break;
         K(0) K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) K(10) K(11) K(12) K(13) K(14) K(15)
         K(F_ALL | F_PROJ) K(F_ALL | F_PROJ | F_TEX)
@@ -3916,11 +4102,29 @@ hipError_t launch_trace(const DevScene& S, int flags, uint32_t samples, const Wo
     return hipGetLastError();
 }
 
-hipError_t launch_reduce(const double* part, double* sums, const WorkPlan& WP, int W, int H, bool planes,
+hipError_t launch_reduce(const double* part, double* sums, const WorkPlan& WP, int W, int H, bool planes, double* sq,
                          hipStream_t st) {
     if (WP.n_tail == 0) return hipSuccess;
-    hipLaunchKernelGGL(reduce_chunks_kernel, dim3((WP.n_tail * 64 + 255) / 256), dim3(256), 0, st, part, sums, WP, W,
-                       H, planes);
+    const dim3 grid((WP.n_tail * 64 + 255) / 256);
+    if (sq)
+        hipLaunchKernelGGL(reduce_chunks_kernel<true>, grid, dim3(256), 0, st, part, sums, WP, W, H, planes, sq);
+    else
+        hipLaunchKernelGGL(reduce_chunks_kernel<false>, grid, dim3(256), 0, st, part, sums, WP, W, H, planes, sq);
+    return hipGetLastError();
+}
+
+// tile_part: 4 doubles per tile of scratch (ptmi_api.cpp ptmi_error_map).
+hipError_t launch_error_map(const double* sums, const double* sq, uint32_t W, uint32_t H, double* se, double* tile_err,
+                            double* tile_part, double* stats, hipStream_t st) {
+    const uint32_t tiles = ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
+    hipLaunchKernelGGL(error_map, dim3(tiles), dim3(64), 0, st, sums, sq, (int)W, (int)H, se, tile_err, tile_part);
+    hipLaunchKernelGGL(error_stats, dim3(1), dim3(256), 0, st, tile_part, tiles, stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(accumulate_sums, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, src, n);
     return hipGetLastError();
 }
 

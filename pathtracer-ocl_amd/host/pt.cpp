@@ -11,14 +11,24 @@
 // --split sample|tile (ptmi_trace_multi over devices 0..N-1), --seed N
 // (per-pixel seeds from a fixed stream; default: time-seeded like Go's
 // rand.Float64 per pixel, ocltracer.go:260-263).
+// Noise target (one GPU): --noise-target X renders batches of --batch B samples (default 64) of
+// the --samples-spp frame through the resident-scene API (ptmi_scene_render_moments,
+// ptmi_accumulate, ptmi_error_map) and stops after the first batch whose relative noise -- rms
+// standard error of the pixel means over the mean pixel value -- is at most X, or when the samples
+// run out; it prints samples_done and the final relative error.  --error-map FILE writes the
+// standard-error map as a .raw image (one channel replicated to R, G, B).
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_host.h"
@@ -32,6 +42,10 @@ struct Cfg {
     int gpus = 1;
     bool list_devices = false, list_scenes = false, have_seed = false;
     uint64_t seed = 0;
+    bool have_target = false;
+    double noise_target = 0.0;
+    int batch = 64;
+    std::string error_map;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -39,7 +53,7 @@ struct Cfg {
                  "%s\nusage: pt [--width N] [--height N] [--samples N] [--aperture F] [--focal-length F]\n"
                  "          [--scene NAME] [--device-index N] [--list-devices] [--list-scenes]\n"
                  "          [--assets DIR] [--out FILE.png] [--raw FILE.raw] [--gpus N] [--split sample|tile]\n"
-                 "          [--seed N]\n",
+                 "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n",
                  msg);
     std::exit(2);
 }
@@ -75,11 +89,85 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--gpus") c.gpus = std::atoi(val().c_str());
         else if (a == "--split") c.split = val();
         else if (a == "--seed") c.seed = std::strtoull(val().c_str(), nullptr, 10), c.have_seed = true;
+        else if (a == "--noise-target") c.noise_target = std::atof(val().c_str()), c.have_target = true;
+        else if (a == "--batch") c.batch = std::atoi(val().c_str());
+        else if (a == "--error-map") c.error_map = val();
+        else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
     if (c.width <= 0 || c.height <= 0 || c.samples <= 0) usage("width, height and samples must be positive");
     if (c.gpus <= 0 || (c.split != "sample" && c.split != "tile")) usage("--gpus must be >= 1, --split sample|tile");
+    if ((c.have_target || !c.error_map.empty()) && c.gpus > 1)
+        usage("--noise-target and --error-map need --gpus 1");
+    if (c.batch <= 0 || (c.have_target && !(c.noise_target >= 0.0))) usage("--batch must be positive, --noise-target >= 0");
     return c;
+}
+
+// The noise-target loop (ptmi/error.py render_to_noise in C): batches [k * batch, (k + 1) * batch) of
+// the samples-spp frame until stats[0] <= target * stats[2].  Without a target (--error-map alone)
+// it renders every sample.  out: RGBA of the samples done; se: the standard-error map as RGBA.
+int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, uint64_t stream_seed,
+                 std::vector<double>& out, std::vector<double>& se_rgba, uint32_t& done, double& rel, char* err,
+                 size_t err_len) {
+    const size_t n = (size_t)c.width * c.height;
+    ptmi_scene* sc = nullptr;
+    double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *b_sums = nullptr, *b_sq = nullptr, *se = nullptr,
+           *stats = nullptr;
+    int rc = ptmi_scene_create_textured(c.device_index, r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp,
+                                        r.camera, tex, &sc, err, err_len);
+    if (rc) return rc;
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return false;
+        std::snprintf(err, err_len, "%s failed: %s", what, hipGetErrorString(e));
+        rc = PTMI_ERR_HIP;
+        return true;
+    };
+    const uint32_t samples = (uint32_t)c.samples;
+    std::vector<double> se_host(n);
+    double st[4] = {0, 0, 0, 0};
+    done = 0;
+    rel = 0.0;
+    do {
+        if (hip(hipSetDevice(c.device_index), "hipSetDevice")) break;
+        if (hip(hipMalloc((void**)&seeds, n * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMalloc((void**)&sums, n * 4 * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMalloc((void**)&sq, n * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMalloc((void**)&b_sums, n * 4 * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMalloc((void**)&b_sq, n * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMalloc((void**)&se, n * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMalloc((void**)&stats, 4 * sizeof(double)), "hipMalloc")) break;
+        if (hip(hipMemset(sums, 0, n * 4 * sizeof(double)), "hipMemset")) break;
+        if (hip(hipMemset(sq, 0, n * sizeof(double)), "hipMemset")) break;
+        if ((rc = ptmi_fill_seeds(seeds, (uint32_t)n, stream_seed, nullptr, err, err_len))) break;
+        while (done < samples) {
+            const uint32_t end = std::min<uint64_t>((uint64_t)done + (uint32_t)c.batch, samples);
+            if ((rc = ptmi_scene_render_moments(sc, samples, done, end, 1, 0, seeds, b_sums, b_sq, 0, nullptr, err,
+                                                err_len)))
+                break;
+            if ((rc = ptmi_accumulate(sums, b_sums, n * 4, nullptr, err, err_len))) break;
+            if ((rc = ptmi_accumulate(sq, b_sq, n, nullptr, err, err_len))) break;
+            if ((rc = ptmi_error_map(sums, sq, (uint32_t)c.width, (uint32_t)c.height, se, nullptr, stats, nullptr, err,
+                                     err_len)))
+                break;
+            if (hip(hipMemcpy(st, stats, sizeof(st), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+            done = end;
+            rel = st[2] != 0.0 ? st[0] / st[2] : HUGE_VAL;
+            if (c.have_target && st[0] <= c.noise_target * st[2]) break;
+        }
+        if (rc) break;
+        if ((rc = ptmi_finalize(sums, sums, (uint32_t)n, done, nullptr, err, err_len))) break;
+        if (hip(hipMemcpy(out.data(), sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+        if (hip(hipMemcpy(se_host.data(), se, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+    } while (false);
+    for (double* p : {seeds, sums, sq, b_sums, b_sq, se, stats})
+        if (p) (void)hipFree(p);
+    ptmi_scene_destroy(sc);
+    se_rgba.resize(n * 4);
+    for (size_t i = 0; i < n; i++) {
+        se_rgba[4 * i + 0] = se_rgba[4 * i + 1] = se_rgba[4 * i + 2] = se_host[i];
+        se_rgba[4 * i + 3] = 1.0;
+    }
+    return rc;
 }
 
 bool known_scene(const std::string& s) {
@@ -133,7 +221,14 @@ int main(int argc, char** argv) {
     const uint64_t stream =
         c.have_seed ? c.seed : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
     ptmi_multi_timing mt{};
-    if (c.gpus == 1) {
+    const bool noise = c.have_target || !c.error_map.empty();
+    std::vector<double> se_rgba;
+    uint32_t samples_done = (uint32_t)c.samples;
+    double rel_err = 0.0;
+    if (noise) {
+        rc = render_noise(c, r, textured ? &tex : nullptr, stream, out, se_rgba, samples_done, rel_err, err,
+                          sizeof(err));
+    } else if (c.gpus == 1) {
         rc = ptmi_trace(r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp, c.device_index,
                         (uint32_t)c.samples, r.camera, nullptr, stream, textured ? &tex : nullptr, out.data(), err,
                         sizeof(err));
@@ -162,11 +257,17 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s\n", err);
         return 1;
     }
+    if (!c.error_map.empty() &&
+        (rc = ptmi_host_write_raw(c.error_map.c_str(), se_rgba.data(), c.width, c.height, err, sizeof(err)))) {
+        std::fprintf(stderr, "%s\n", err);
+        return 1;
+    }
+    if (noise) std::printf("samples_done %u relative_error %.6g\n", samples_done, rel_err);
     const double build_s = std::chrono::duration<double>(t1 - t0).count();
     const double trace_s = std::chrono::duration<double>(t2 - t1).count();
     std::fprintf(stderr, "scene %s built in %.3f s; %dx%d x %d spp traced in %.3f s (%.1f Msamples/s); wrote %s\n",
-                 scene.c_str(), build_s, c.width, c.height, c.samples, trace_s,
-                 (double)n * c.samples / trace_s / 1e6, png.c_str());
+                 scene.c_str(), build_s, c.width, c.height, (int)samples_done, trace_s,
+                 (double)n * samples_done / trace_s / 1e6, png.c_str());
     if (c.gpus > 1)
         std::fprintf(stderr,
                      "%d GPUs (%s split): prepare %.3f ms, render %.3f ms, combine %.3f ms, read-back %.3f ms\n",

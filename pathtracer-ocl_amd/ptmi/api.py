@@ -37,7 +37,7 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_scene_size", "ptmi_scene_render", "ptmi_finalize", "ptmi_fill_seeds", "ptmi_build_info",
            "ptmi_scene_set_timing", "ptmi_scene_kernel_time", "ptmi_trace_multi", "ptmi_scene_create_textured",
            "ptmi_trace_multi_timed", "ptmi_sample_split_point", "ptmi_combine_frames",
-           "ptmi_scene_set_rng", "ptmi_index_stats")
+           "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate")
 
 
 class MultiTiming(ctypes.Structure):
@@ -97,6 +97,13 @@ def load_library(path=None):
     lib.ptmi_scene_size.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     lib.ptmi_scene_render.restype = i32
     lib.ptmi_scene_render.argtypes = [vp, u32, u32, u32, u32, u32, vp, vp, u32, vp, cp, sz]
+    if hasattr(lib, "ptmi_scene_render_moments"):  # (diagnostic libraries of earlier rounds lack them)
+        lib.ptmi_scene_render_moments.restype = i32
+        lib.ptmi_scene_render_moments.argtypes = [vp, u32, u32, u32, u32, u32, vp, vp, vp, u32, vp, cp, sz]
+        lib.ptmi_error_map.restype = i32
+        lib.ptmi_error_map.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, cp, sz]
+        lib.ptmi_accumulate.restype = i32
+        lib.ptmi_accumulate.argtypes = [vp, vp, sz, vp, cp, sz]
     lib.ptmi_finalize.restype = i32
     lib.ptmi_finalize.argtypes = [vp, vp, u32, u32, vp, cp, sz]
     lib.ptmi_fill_seeds.restype = i32
@@ -282,6 +289,17 @@ class Scene:
                                          ctypes.c_void_p(stream), err, len(err))
         _check(rc, err)
 
+    def render_moments(self, samples, sample_begin, sample_end, seeds_ptr, sums_ptr, sq_ptr, tile_stride=1,
+                       tile_offset=0, chunks=0, stream=0):
+        """ptmi_scene_render_moments: render(), also writing sq_ptr[W*H] -- per owned pixel the sum over
+        the range's paths of (r*r + g*g) + b*b, 0 elsewhere.  The sums are render()'s bit for bit."""
+        err = ctypes.create_string_buffer(1024)
+        rc = self._lib.ptmi_scene_render_moments(self._h, samples, sample_begin, sample_end, tile_stride, tile_offset,
+                                                 ctypes.c_void_p(seeds_ptr), ctypes.c_void_p(sums_ptr),
+                                                 ctypes.c_void_p(sq_ptr), chunks, ctypes.c_void_p(stream), err,
+                                                 len(err))
+        _check(rc, err)
+
     def finalize(self, sums_ptr, out_ptr, samples, stream=0):
         err = ctypes.create_string_buffer(1024)
         rc = self._lib.ptmi_finalize(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(out_ptr),
@@ -353,3 +371,23 @@ def fill_seeds(seeds_ptr, n, seed_stream, stream=0):
     err = ctypes.create_string_buffer(256)
     _check(lib.ptmi_fill_seeds(ctypes.c_void_p(seeds_ptr), n, seed_stream, ctypes.c_void_p(stream), err, len(err)),
            err)
+
+
+def error_map(sums_ptr, sq_ptr, width, height, stats_ptr, se_ptr=0, tile_err_ptr=0, stream=0):
+    """ptmi_error_map: from frame sums (W*H*4: r, g, b, n) and second moments (W*H), the standard
+    error of each pixel's mean into se_ptr (W*H doubles, optional), each 8x8 tile's rms standard
+    error into tile_err_ptr (raster order, optional) and stats_ptr[4] = (rms standard error, largest
+    finite one, mean of the pixel means, pixel count) over the pixels with n >= 2.  The formula is
+    ptmi/error.py error_map_reference."""
+    err = ctypes.create_string_buffer(256)
+    _check(load_library().ptmi_error_map(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(sq_ptr), int(width), int(height),
+                                         ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(tile_err_ptr or None),
+                                         ctypes.c_void_p(stats_ptr), ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def accumulate(dst_ptr, src_ptr, n, stream=0):
+    """ptmi_accumulate: dst[k] += src[k] over n doubles of device memory (batches of sums, whose
+    fourth slots -- the sample counts -- add too, and of second moments)."""
+    err = ctypes.create_string_buffer(256)
+    _check(load_library().ptmi_accumulate(ctypes.c_void_p(dst_ptr), ctypes.c_void_p(src_ptr), int(n),
+                                          ctypes.c_void_p(stream), err, len(err)), err)
