@@ -203,6 +203,48 @@ int ptmi_scene_render_moments(ptmi_scene* s, uint32_t samples, uint32_t sample_b
                               char* err, size_t err_len);
 
 /*
+ * ptmi_scene_render_moments on a caller's list of 8x8 tiles (per-tile adaptive sampling):
+ * tiles_dev holds n_tiles distinct raster indices of tiles, in device memory.  sums_dev
+ * (W*H*4) and sq_dev (W*H, required) are OVERWRITTEN: the listed tiles' pixels get what
+ * ptmi_scene_render_moments(..., tile_stride 1, tile_offset 0, the same chunks) gives them
+ * (bit for bit with an explicit chunk count; with chunks = 0 the plan depends on the
+ * number of tiles, so the sums may differ by FP64 regrouping), every other pixel 0.  An
+ * index >= the frame's tile count is skipped; duplicate entries are undefined behaviour.
+ * n_tiles == 0 zeroes both buffers and launches no trace kernel; tiles_dev == NULL with
+ * n_tiles > 0 is PTMI_ERR_ARG.  The work items run in list order (the costliest-first
+ * dispatch order of mesh scenes is built for the library's own tile ownership only).
+ * Asynchronous on the stream; timing, the RNG mode and the 2^26 pooled-item guard apply
+ * as to ptmi_scene_render_moments.
+ */
+int ptmi_scene_render_tiles(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
+                            const uint32_t* tiles_dev, uint32_t n_tiles, const double* seeds_dev,
+                            double* sums_dev, double* sq_dev, uint32_t chunks, void* hip_stream, char* err,
+                            size_t err_len);
+
+/*
+ * The tiles that still need samples: an order-preserving compaction of the candidates
+ * in_tiles_dev[0..n_in) (in_tiles_dev == NULL: tiles 0..n_in themselves; n_in <= 2^31).
+ * Candidate t is kept iff tile_err_dev[t] > threshold: a NaN error is dropped (it would
+ * never converge), +inf is kept, an error equal to the threshold is dropped.  Every
+ * candidate must index tile_err_dev.  The kept tiles go to out_tiles_dev (room for n_in
+ * entries) in candidate order, their number to count_dev[0]; n_in == 0 writes count 0.
+ * out_tiles_dev must not alias in_tiles_dev (callers ping-pong two buffers).  One
+ * workgroup, no atomics: equal inputs give equal lists.  Asynchronous on the stream.
+ */
+int ptmi_select_tiles(const double* tile_err_dev, const uint32_t* in_tiles_dev, uint32_t n_in,
+                      double threshold, uint32_t* out_tiles_dev, uint32_t* count_dev, void* hip_stream,
+                      char* err, size_t err_len);
+
+/*
+ * ptmi_finalize by each pixel's own sample count n = sums_dev[4i+3] (frames whose tiles
+ * stopped at different counts): n == 0 -> RGB 0, otherwise RGB = sum_c * (1.0 / n), the
+ * same multiply as ptmi_finalize, so a uniform count gives its output bit for bit; A = 1.0.
+ * out_dev must not alias sums_dev.
+ */
+int ptmi_finalize_counts(const double* sums_dev, double* out_dev, uint32_t n_pixels, void* hip_stream,
+                         char* err, size_t err_len);
+
+/*
  * The standard error of each pixel's mean from frame sums (r, g, b, n per pixel)
  * and second moments.  Per pixel i, n = sums_dev[4i+3]:
  *   n == 0: se = 0 (not owned);  n == 1: se = +inf;  otherwise

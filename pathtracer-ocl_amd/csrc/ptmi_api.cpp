@@ -42,6 +42,9 @@ hipError_t launch_error_map(const double* sums, const double* sq, uint32_t W, ui
                             double* tile_part, double* stats, hipStream_t st);
 hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream_t st);
 hipError_t launch_finalize(const double* sums, double* out, uint32_t npix, uint32_t samples, hipStream_t st);
+hipError_t launch_finalize_counts(const double* sums, double* out, uint32_t npix, hipStream_t st);
+hipError_t launch_select_tiles(const double* tile_err, const uint32_t* in_tiles, uint32_t n_in, double threshold,
+                               uint32_t* out_tiles, uint32_t* count, hipStream_t st);
 hipError_t launch_seeds(double* seeds, uint32_t n, uint64_t stream, hipStream_t st);
 hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st);
 hipError_t launch_hemi_table(double* out, int* mismatch, hipStream_t st);
@@ -933,9 +936,12 @@ static bool diagonal_tiles(const ptmi_scene* s, uint32_t tile_stride) {
 
 // ptmi_scene_render (sq_dev == nullptr) and ptmi_scene_render_moments (sq_dev: W*H second moments):
 // one plan for both, so the moment render's colour sums are the plain render's bit for bit.
+// list_dev (ptmi_scene_render_tiles; tile_stride 1, tile_offset 0, sq_dev set): the owned tiles are the
+// caller's n_list device-resident raster indices instead, planned by the same code.
 static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
                         uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev, double* sums_dev,
-                        double* sq_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len) {
+                        double* sq_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len,
+                        const uint32_t* list_dev = nullptr, uint32_t n_list = 0) {
     if (!s || !seeds_dev || !sums_dev || samples == 0 || sample_begin > sample_end || sample_end > samples ||
         tile_stride == 0 || tile_offset >= tile_stride) {
         set_err(err, err_len, "bad render arguments (samples %u range [%u,%u) tiles %u/%u)", samples, sample_begin,
@@ -955,14 +961,16 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
     // tile (x, y) belongs to rank (x + y) mod stride, each row holding tiles_x / stride of a
     // rank's tiles -- through the F_TLIST instantiations (WorkPlan::tiles), so the one-GPU
     // kernels are untouched (profiles/r5/tile_skew).  Every pixel's sums are the same either way.
-    const bool tlist = diagonal_tiles(s, tile_stride);
+    const bool tlist = !list_dev && diagonal_tiles(s, tile_stride);
     const uint32_t per_row = tiles_x / tile_stride;
     auto owned_tile = [&](uint32_t k) -> uint32_t {
         if (!tlist) return tile_offset + k * tile_stride;
         const uint32_t ty = k / per_row, j = k - ty * per_row;
         return ty * tiles_x + (tile_offset + tile_stride - ty % tile_stride) % tile_stride + j * tile_stride;
     };
-    const uint32_t owned_tiles = tlist ? tiles / tile_stride : (tiles + tile_stride - 1 - tile_offset) / tile_stride;
+    const uint32_t owned_tiles = list_dev ? n_list
+                                 : tlist  ? tiles / tile_stride
+                                          : (tiles + tile_stride - 1 - tile_offset) / tile_stride;
     // Work items (WorkPlan, ptmi_device.h).  Automatic (chunks == 0), scenes without
     // meshes: whole tiles first, then the last ~0.5 resident waves' worth of tiles
     // split into sample chunks, so that short items fill the end of the launch (~6 per
@@ -985,7 +993,9 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
     // Affine mesh scenes in parity mode, when the split form is selected (render_split): pixel-chunks of
     // split_chunk samples (an explicit `chunks` sets the chunk count as for the one-kernel
     // form, so both forms then sum the same chunks in the same order).
-    const int kflags = kflags0 | (tlist ? 128 : 0);  // F_TLIST
+    // (a caller's list: the F_TLIST instantiations where the scene's family has them, else the moment
+    // instantiation's own select on WorkPlan::tiles, ptmi_kernels.hip kTilesOf)
+    const int kflags = kflags0 | ((tlist || (list_dev && tile_list_supported(kflags0))) ? 128 : 0);  // F_TLIST
 #if PTMI_STUDY
     const bool split = s->split && split_supported(kflags) && range > 0;
 #else
@@ -1029,7 +1039,7 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
                                               std::max<uint32_t>(range / floor, 1));
     }
     // The path pool of the tile-list kernels numbers an item's paths 64 x its samples in 32 bits.
-    if (tlist) chunks = std::max<uint32_t>(chunks, (range + (1u << 25) - 1) >> 25);
+    if (kflags & 128) chunks = std::max<uint32_t>(chunks, (range + (1u << 25) - 1) >> 25);
     chunks = std::max<uint32_t>(1, std::min<uint32_t>(chunks, std::max<uint32_t>(range, 1)));
     const uint32_t chunk_len = range == 0 ? 1 : (range + chunks - 1) / chunks;
     chunks = range == 0 ? 1 : (range + chunk_len - 1) / chunk_len;
@@ -1085,6 +1095,10 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
         }
         wp.tiles = s->tlist_dev;
     }
+    // A caller's list lives on the device: the library's cached diagonal list and its cached
+    // dispatch order (both built on the host from its own ownership) are left alone, and the items
+    // run in list order.  (A costliest-first order of listed tiles would need the list on the host.)
+    if (list_dev) wp.tiles = list_dev;
     if (sq_dev) {
 #if PTMI_STUDY
         if (split) {
@@ -1101,7 +1115,7 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
         }
     }
     const bool mesh_plan = (s->flags & 1) != 0;  // F_GROUPS
-    if (!split && s->tile_order && owned_tiles > 0 && mesh_plan) {
+    if (!split && s->tile_order && owned_tiles > 0 && mesh_plan && !list_dev) {
         // Mesh scenes: the dispatch order of the work items -- whole tiles among themselves,
         // then each chunk round's tiles among themselves (which tiles are whole and which
         // chunked stays the raster-defined plan above, so no pixel's sums change).  A rank's
@@ -1169,8 +1183,9 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
             }
         }
     }
-    if (tile_stride > 1) HIP_TRY(hipMemsetAsync(sums_dev, 0, (size_t)npix * 4 * sizeof(double), st));  // un-owned tiles
-    if (tile_stride > 1 && sq_dev) HIP_TRY(hipMemsetAsync(sq_dev, 0, (size_t)npix * sizeof(double), st));
+    const bool partial_frame = tile_stride > 1 || list_dev;  // un-owned tiles
+    if (partial_frame) HIP_TRY(hipMemsetAsync(sums_dev, 0, (size_t)npix * 4 * sizeof(double), st));
+    if (partial_frame && sq_dev) HIP_TRY(hipMemsetAsync(sq_dev, 0, (size_t)npix * sizeof(double), st));
     const bool planes = (s->flags & 1) == 0 || (PTMI_MESH_PLANES && !split);  // partial layout (ptmi_kernels.hip store_sums)
     // (moment renders: one more plane of partials, ptmi_kernels.hip store_mom)
     const size_t need = (size_t)wp.n_tail * 64 * chunks * ((planes ? 3 : 4) + (sq_dev ? 1 : 0)) * sizeof(double);
@@ -1229,6 +1244,57 @@ int ptmi_scene_render_moments(ptmi_scene* s, uint32_t samples, uint32_t sample_b
     }
     return render_frame(s, samples, sample_begin, sample_end, tile_stride, tile_offset, seeds_dev, sums_dev, sq_dev,
                         chunks, hip_stream, err, err_len);
+}
+
+int ptmi_scene_render_tiles(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, uint32_t sample_end,
+                            const uint32_t* tiles_dev, uint32_t n_tiles, const double* seeds_dev, double* sums_dev,
+                            double* sq_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len) {
+    if (!s || !sums_dev || !sq_dev || (!tiles_dev && n_tiles > 0)) {
+        set_err(err, err_len, "ptmi_scene_render_tiles: scene, sums_dev or sq_dev == NULL, or %u tiles without a list",
+                n_tiles);
+        return PTMI_ERR_ARG;
+    }
+    if (n_tiles == 0) {  // no tile owned: the two frames are zero, and no plan is made
+        if (!seeds_dev || samples == 0 || sample_begin > sample_end || sample_end > samples) {
+            set_err(err, err_len, "bad render arguments (samples %u range [%u,%u))", samples, sample_begin, sample_end);
+            return PTMI_ERR_ARG;
+        }
+        HIP_TRY(hipSetDevice(s->device));
+        const size_t npix = (size_t)s->width * s->height;
+        HIP_TRY(hipMemsetAsync(sums_dev, 0, npix * 4 * sizeof(double), (hipStream_t)hip_stream));
+        HIP_TRY(hipMemsetAsync(sq_dev, 0, npix * sizeof(double), (hipStream_t)hip_stream));
+        return PTMI_OK;
+    }
+#if PTMI_STUDY
+    if (s->split) {
+        set_err(err, err_len, "the split execution form takes no tile list");
+        return PTMI_ERR_UNSUPPORTED;
+    }
+#endif
+    return render_frame(s, samples, sample_begin, sample_end, 1, 0, seeds_dev, sums_dev, sq_dev, chunks, hip_stream,
+                        err, err_len, tiles_dev, n_tiles);
+}
+
+int ptmi_select_tiles(const double* tile_err_dev, const uint32_t* in_tiles_dev, uint32_t n_in, double threshold,
+                      uint32_t* out_tiles_dev, uint32_t* count_dev, void* hip_stream, char* err, size_t err_len) {
+    if (!count_dev || (n_in > 0 && (!tile_err_dev || !out_tiles_dev)) || n_in > (1u << 31) ||
+        (n_in > 0 && out_tiles_dev == in_tiles_dev)) {
+        set_err(err, err_len, "bad select-tiles arguments (%u candidates)", n_in);
+        return PTMI_ERR_ARG;
+    }
+    HIP_TRY(launch_select_tiles(tile_err_dev, in_tiles_dev, n_in, threshold, out_tiles_dev, count_dev,
+                                (hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
+int ptmi_finalize_counts(const double* sums_dev, double* out_dev, uint32_t n_pixels, void* hip_stream, char* err,
+                         size_t err_len) {
+    if (!sums_dev || !out_dev) {
+        set_err(err, err_len, "bad finalize arguments");
+        return PTMI_ERR_ARG;
+    }
+    HIP_TRY(launch_finalize_counts(sums_dev, out_dev, n_pixels, (hipStream_t)hip_stream));
+    return PTMI_OK;
 }
 
 int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width, uint32_t height, double* se_dev,

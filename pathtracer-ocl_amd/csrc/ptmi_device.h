@@ -264,7 +264,9 @@ struct WorkPlan {
     unsigned long long* cost;
     // Optional owned-tile list (tile-split launches of the affine mesh kernels, the F_TLIST
     // instantiations): owned tile k is tiles[k] (raster index) instead of tile_offset +
-    // k * tile_stride.  nullptr in every other launch.
+    // k * tile_stride.  Also a caller's list (ptmi_scene_render_tiles): those instantiations, or
+    // the F_MOM instantiation of a family without them, which selects on this pointer
+    // (ptmi_kernels.hip kTilesOf).  nullptr in every other launch.
     const uint32_t* tiles;
 };
 

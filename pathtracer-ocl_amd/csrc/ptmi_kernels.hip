@@ -2223,9 +2223,18 @@ __device__ __forceinline__ void chunk_range(const WorkPlan& WP, uint32_t c, uint
     c0 = WP.s_begin + (lng ? c * WP.chunk_len : WP.n_long * WP.chunk_len + (c - WP.n_long) * WP.tail_len);
     c1 = min(WP.s_end, c0 + (lng ? WP.chunk_len : WP.tail_len));
 }
-// kList (F_TLIST instantiations): owned tile k is WP.tiles[k] (a scalar load of a uniform
-// index) instead of tile_offset + k * tile_stride.
-template <bool kList = false>
+// Where owned tile k comes from (kTilesOf<FL>).  kTilesStride: tile_offset + k * tile_stride.
+// kTilesList (F_TLIST instantiations): WP.tiles[k], a scalar load of a uniform index.
+// kTilesSelect (the F_MOM instantiations of the families without F_TLIST forms): the list when the
+// launch has one (ptmi_scene_render_tiles), else the stride -- a wave-uniform select, so the plain
+// instantiations, which never take a caller's list, keep their code.
+enum : int { kTilesStride = 0, kTilesList = 1, kTilesSelect = 2 };
+template <int FL>
+constexpr int kTilesOf = (FL & F_TLIST) ? kTilesList
+                         : ((FL & F_MOM) && !((FL & F_GROUPS) && !(FL & (F_PROJ | F_TEX | F_XRNG | F_WIDE))))
+                             ? kTilesSelect
+                             : kTilesStride;
+template <int kTiles = kTilesStride>
 __device__ __forceinline__ Item work_item(const DevScene& S, const WorkPlan& WP, uint32_t item, int lane) {
     Item it{};
     const int W = S.cam.width, H = S.cam.height;
@@ -2247,7 +2256,13 @@ __device__ __forceinline__ Item work_item(const DevScene& S, const WorkPlan& WP,
         chunk_range(WP, c, it.c0, it.c1);
         it.oslot = ((size_t)c * WP.n_tail + tt) * 64 + lane;
     }
-    const uint32_t tile = kList ? WP.tiles[k] : WP.tile_offset + k * WP.tile_stride;
+    uint32_t tile;
+    if constexpr (kTiles == kTilesList)
+        tile = WP.tiles[k];
+    else if constexpr (kTiles == kTilesSelect)
+        tile = WP.tiles ? WP.tiles[k] : WP.tile_offset + k * WP.tile_stride;
+    else
+        tile = WP.tile_offset + k * WP.tile_stride;
     if (tile >= (uint32_t)(tiles_x * tiles_y)) return it;
     it.px = (int)(tile % (uint32_t)tiles_x) * kTile + (lane & 7);
     it.py = (int)(tile / (uint32_t)tiles_x) * kTile + (lane >> 3);
@@ -2413,7 +2428,7 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
 #if PTMI_STATS
     ptmi_wstat[0][lane] = 0;
 #endif
-    const Item it = work_item<(FL & F_TLIST) != 0>(S, WP, item, lane);
+    const Item it = work_item<kTilesOf<FL>>(S, WP, item, lane);
     if (!it.ok) return;
     const int px = it.px, py = it.py;
     // fgi / fgi2 (tracer.cl:839-841): double division rounded to float.
@@ -2595,9 +2610,9 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
 #endif
     // The work item is re-derived (a few integer operations) rather than kept live across
     // the loop: its fields would hold ~5 VGPRs through every walk phase.
-    store_sums<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S, WP, item, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock], acc[2 * kBlock]);
+    store_sums<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S, WP, item, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock], acc[2 * kBlock]);
     if constexpr (kMom)
-        store_mom<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S, WP, item, lane), WP, sq, part, m2[0]);
+        store_mom<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S, WP, item, lane), WP, sq, part, m2[0]);
 }
 
 // trace_groups with the path pool (kPoolOf above): the same loop, phases and walks; what
@@ -2629,7 +2644,7 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
 #if PTMI_STATS
     ptmi_wstat[0][lane] = 0;
 #endif
-    const Item it = work_item<(FL & F_TLIST) != 0>(S0, WP, item, lane);
+    const Item it = work_item<kTilesOf<FL>>(S0, WP, item, lane);
     if (!it.ok) return;
     const double seed0 = it.inside ? seeds[it.i] : 0.0;
     fgi_lds[tid] = (float)(seed0 / (double)S0.n_list);
@@ -2760,10 +2775,10 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
         }
     }
     __builtin_amdgcn_wave_barrier();
-    store_sums<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S0, WP, item, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
+    store_sums<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S0, WP, item, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
                                       acc_lds[1 * kBlock + tid], acc_lds[2 * kBlock + tid]);
     if constexpr (kMom)
-        store_mom<PTMI_MESH_PLANES != 0>(work_item<(FL & F_TLIST) != 0>(S0, WP, item, lane), WP, sq, part, m2_lds[tid]);
+        store_mom<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S0, WP, item, lane), WP, sq, part, m2_lds[tid]);
 }
 
 // The path pool for the kernels without meshes (PTMI_POOL_FLAT, affine non-DoF parity-mode scenes):
@@ -2797,7 +2812,7 @@ __device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t sam
     __shared__ float fgi_lds[kBlock];
     __shared__ float fgi2_lds[PTMI_POOL_FGI2_SEED ? 1 : kBlock];
     const int tid = threadIdx.x, lane = tid & 63;
-    const Item it = work_item(S0, WP, blockIdx.x, lane);
+    const Item it = work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane);
     if (!it.ok) return;
     {
         const double seed0 = it.inside ? seeds[it.i] : 0.0;
@@ -2895,9 +2910,9 @@ __device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t sam
         }
     }
     __builtin_amdgcn_wave_barrier();
-    store_sums<true>(work_item(S0, WP, blockIdx.x, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
+    store_sums<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
                      acc_lds[1 * kBlock + tid], acc_lds[2 * kBlock + tid]);
-    if constexpr (kMom) store_mom<true>(work_item(S0, WP, blockIdx.x, lane), WP, sq, part, m2_lds[tid]);
+    if constexpr (kMom) store_mom<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sq, part, m2_lds[tid]);
 }
 
 // Per-item duration onto its tile's cost accumulator (WorkPlan::cost, tile_order_kernel;
@@ -2972,7 +2987,7 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
 #if PTMI_STATS
     ptmi_wstat[0][lane] = 0;
 #endif
-    const Item it = work_item(S0, WP, blockIdx.x, lane);
+    const Item it = work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane);
     if (!it.ok) return;
     const int px = it.px, py = it.py;
     // fgi / fgi2 (tracer.cl:839-841): double division rounded to float.
@@ -3060,9 +3075,9 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
         for (int k = 0; k < 64; k++)
             if (ptmi_wstat[0][k]) atomicAdd(&ptmi_stats[k], ptmi_wstat[0][k]);
 #endif
-    store_sums<true>(work_item(S0, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
+    store_sums<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
                      acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
-    if constexpr (kMom) store_mom<true>(work_item(S0, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
+    if constexpr (kMom) store_mom<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
 }
 
 template <int FL>
@@ -3113,7 +3128,7 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
 #if PTMI_STATS
         ptmi_wstat[0][lane] = 0;
 #endif
-        const Item it = work_item(S, WP, blockIdx.x, lane);
+        const Item it = work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane);
         if (!it.ok) return;
         const int px = it.px, py = it.py;
         // fgi / fgi2 (tracer.cl:839-841): double division rounded to float.
@@ -3266,9 +3281,9 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
             for (int k = 0; k < 64; k++)
                 if (ptmi_wstat[0][k]) atomicAdd(&ptmi_stats[k], ptmi_wstat[0][k]);
 #endif
-        store_sums<true>(work_item(S, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
+        store_sums<true>(work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
                    acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
-        if constexpr (kMom) store_mom<true>(work_item(S, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
+        if constexpr (kMom) store_mom<true>(work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
 #if PTMI_TIMELINE
         if (threadIdx.x == 0 && blockIdx.x < ptmi_tl_max) {
             ptmi_tl[2 * blockIdx.x] = tl0;
@@ -3854,6 +3869,7 @@ __global__ __launch_bounds__(256) void reduce_chunks_kernel(const double* __rest
     const int tiles_x = (W + kTile - 1) / kTile;
     const uint32_t k = WP.n_whole + tt;
     const uint32_t tile = WP.tiles ? WP.tiles[k] : WP.tile_offset + k * WP.tile_stride;
+    if (tile >= (uint32_t)tiles_x * (uint32_t)((H + kTile - 1) / kTile)) return;  // a caller's list: as work_item
     const int px = (int)(tile % (uint32_t)tiles_x) * kTile + (int)(lane & 7);
     const int py = (int)(tile / (uint32_t)tiles_x) * kTile + (int)(lane >> 3);
     if (px >= W || py >= H) return;
@@ -4000,6 +4016,60 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double* __restrict_
     out[4 * (size_t)i + 1] = sums[4 * (size_t)i + 1] * w;
     out[4 * (size_t)i + 2] = sums[4 * (size_t)i + 2] * w;
     out[4 * (size_t)i + 3] = 1.0;
+}
+
+// finalize_kernel with each pixel's own sample count n = sums[4i + 3] (adaptive renders): the same
+// multiply by 1.0 / n, so a uniform count gives finalize_kernel's bits; n == 0 -> RGB 0.  Alpha 1.
+__global__ __launch_bounds__(256) void finalize_counts(const double* __restrict__ sums,
+                                                              double* __restrict__ out, uint32_t npix) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const double n = sums[4 * (size_t)i + 3];
+    const double w = 1.0 / n;
+    out[4 * (size_t)i + 0] = n == 0.0 ? 0.0 : sums[4 * (size_t)i + 0] * w;
+    out[4 * (size_t)i + 1] = n == 0.0 ? 0.0 : sums[4 * (size_t)i + 1] * w;
+    out[4 * (size_t)i + 2] = n == 0.0 ? 0.0 : sums[4 * (size_t)i + 2] * w;
+    out[4 * (size_t)i + 3] = 1.0;
+}
+
+// The tiles that still need samples (ptmi_select_tiles): candidate j is in_tiles[j] (or j itself,
+// in_tiles == nullptr), kept iff tile_err[candidate] > threshold -- a NaN error and a tie are
+// dropped, +inf is kept -- and the kept ones go to out_tiles in candidate order, their number to
+// count[0].  One workgroup walks the candidates in blocks of kSelectBlock, in order: each wave
+// ballots its 64 keeps, the waves' counts meet in LDS, and a kept candidate's position is the
+// running base plus the earlier waves' counts plus the kept lanes below it.  No atomic decides a
+// position: equal inputs give equal lists.
+constexpr uint32_t kSelectBlock = 1024;
+__global__ __launch_bounds__(kSelectBlock) void select_tiles(const double* __restrict__ tile_err,
+                                                                    const uint32_t* __restrict__ in_tiles,
+                                                                    uint32_t n_in, double threshold,
+                                                                    uint32_t* __restrict__ out_tiles,
+                                                                    uint32_t* __restrict__ count) {
+    __shared__ uint32_t wave_n[kSelectBlock / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    uint32_t base = 0;
+    for (uint32_t b0 = 0; b0 < n_in; b0 += kSelectBlock) {  // (n_in <= 2^31: b0 + t does not wrap)
+        const uint32_t j = b0 + t;
+        uint32_t tile = 0;
+        bool keep = false;
+        if (j < n_in) {
+            tile = in_tiles ? in_tiles[j] : j;
+            keep = tile_err[tile] > threshold;  // (a NaN compares false)
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_n[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t pos = base, total = 0;
+        for (uint32_t w = 0; w < kSelectBlock / 64; w++) {
+            const uint32_t n = wave_n[w];
+            pos += w < wv ? n : 0u;
+            total += n;
+        }
+        if (keep) out_tiles[pos + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = tile;
+        base += total;
+        __syncthreads();  // wave_n is rewritten by the next block
+    }
+    if (t == 0) count[0] = base;
 }
 
 // ptmi_trace_multi's device-side combine: out = the partial frames parts[0..nparts)
@@ -4175,6 +4245,19 @@ hipError_t launch_tile_order(unsigned long long* cost, uint32_t n_whole, uint32_
 
 hipError_t launch_finalize(const double* sums, double* out, uint32_t npix, uint32_t samples, hipStream_t st) {
     hipLaunchKernelGGL(finalize_kernel, dim3((npix + 255) / 256), dim3(256), 0, st, sums, out, npix, samples);
+    return hipGetLastError();
+}
+
+hipError_t launch_finalize_counts(const double* sums, double* out, uint32_t npix, hipStream_t st) {
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(finalize_counts, dim3((npix + 255) / 256), dim3(256), 0, st, sums, out, npix);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_tiles(const double* tile_err, const uint32_t* in_tiles, uint32_t n_in, double threshold,
+                               uint32_t* out_tiles, uint32_t* count, hipStream_t st) {
+    hipLaunchKernelGGL(select_tiles, dim3(1), dim3(kSelectBlock), 0, st, tile_err, in_tiles, n_in, threshold,
+                       out_tiles, count);
     return hipGetLastError();
 }
 

@@ -17,6 +17,11 @@
 // standard error of the pixel means over the mean pixel value -- is at most X, or when the samples
 // run out; it prints samples_done and the final relative error.  --error-map FILE writes the
 // standard-error map as a .raw image (one channel replicated to R, G, B).
+// --adaptive (with --noise-target): every 8x8 tile stops on its own, once its rms standard error is
+// at most X times the frame's mean pixel value of that batch (ptmi/error.py render_adaptive in C:
+// ptmi_scene_render_tiles, ptmi_select_tiles, ptmi_finalize_counts); samples_done is then the
+// largest per-tile count, and a second line gives the mean samples per pixel and the tiles that
+// ran to --samples.  --sample-map FILE writes the per-pixel sample counts as a .raw image.
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
 #include <algorithm>
 #include <chrono>
@@ -46,6 +51,8 @@ struct Cfg {
     double noise_target = 0.0;
     int batch = 64;
     std::string error_map;
+    bool adaptive = false;
+    std::string sample_map;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -53,7 +60,8 @@ struct Cfg {
                  "%s\nusage: pt [--width N] [--height N] [--samples N] [--aperture F] [--focal-length F]\n"
                  "          [--scene NAME] [--device-index N] [--list-devices] [--list-scenes]\n"
                  "          [--assets DIR] [--out FILE.png] [--raw FILE.raw] [--gpus N] [--split sample|tile]\n"
-                 "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n",
+                 "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n"
+                 "          [--adaptive] [--sample-map FILE.raw]\n",
                  msg);
     std::exit(2);
 }
@@ -92,6 +100,8 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--noise-target") c.noise_target = std::atof(val().c_str()), c.have_target = true;
         else if (a == "--batch") c.batch = std::atoi(val().c_str());
         else if (a == "--error-map") c.error_map = val();
+        else if (a == "--adaptive") c.adaptive = true;
+        else if (a == "--sample-map") c.sample_map = val();
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
@@ -99,6 +109,10 @@ Cfg parse(int argc, char** argv) {
     if (c.gpus <= 0 || (c.split != "sample" && c.split != "tile")) usage("--gpus must be >= 1, --split sample|tile");
     if ((c.have_target || !c.error_map.empty()) && c.gpus > 1)
         usage("--noise-target and --error-map need --gpus 1");
+    if ((c.adaptive || !c.sample_map.empty()) && c.gpus > 1) usage("--adaptive and --sample-map need --gpus 1");
+    if (c.adaptive && !c.have_target) usage("--adaptive needs --noise-target");
+    if (!c.sample_map.empty() && !c.adaptive) usage("--sample-map needs --adaptive");
+    if (c.adaptive && c.batch < 2) usage("--adaptive needs --batch >= 2");
     if (c.batch <= 0 || (c.have_target && !(c.noise_target >= 0.0))) usage("--batch must be positive, --noise-target >= 0");
     return c;
 }
@@ -106,13 +120,19 @@ Cfg parse(int argc, char** argv) {
 // The noise-target loop (ptmi/error.py render_to_noise in C): batches [k * batch, (k + 1) * batch) of
 // the samples-spp frame until stats[0] <= target * stats[2].  Without a target (--error-map alone)
 // it renders every sample.  out: RGBA of the samples done; se: the standard-error map as RGBA.
+// --adaptive: each batch runs on the tiles still above the threshold (two lists, ping-pong), and the
+// frame is finalised by each pixel's own count; counts_rgba: the counts as RGBA, tiles_at_max: the
+// tiles that took every sample.
 int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, uint64_t stream_seed,
-                 std::vector<double>& out, std::vector<double>& se_rgba, uint32_t& done, double& rel, char* err,
-                 size_t err_len) {
+                 std::vector<double>& out, std::vector<double>& se_rgba, uint32_t& done, double& rel,
+                 std::vector<double>& counts_rgba, uint32_t& tiles_at_max, char* err, size_t err_len) {
     const size_t n = (size_t)c.width * c.height;
+    const uint32_t tiles = (uint32_t)((c.width + 7) / 8) * (uint32_t)((c.height + 7) / 8);
     ptmi_scene* sc = nullptr;
     double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *b_sums = nullptr, *b_sq = nullptr, *se = nullptr,
-           *stats = nullptr;
+           *stats = nullptr, *tile_err = nullptr;
+    uint32_t* lists = nullptr;  // adaptive: two tile lists and the selected count behind them
+    tiles_at_max = 0;
     int rc = ptmi_scene_create_textured(c.device_index, r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp,
                                         r.camera, tex, &sc, err, err_len);
     if (rc) return rc;
@@ -139,6 +159,47 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
         if (hip(hipMemset(sums, 0, n * 4 * sizeof(double)), "hipMemset")) break;
         if (hip(hipMemset(sq, 0, n * sizeof(double)), "hipMemset")) break;
         if ((rc = ptmi_fill_seeds(seeds, (uint32_t)n, stream_seed, nullptr, err, err_len))) break;
+        if (c.adaptive) {
+            if (hip(hipMalloc((void**)&tile_err, tiles * sizeof(double)), "hipMalloc")) break;
+            if (hip(hipMalloc((void**)&lists, ((size_t)2 * tiles + 1) * sizeof(uint32_t)), "hipMalloc")) break;
+            std::vector<uint32_t> all(tiles);
+            for (uint32_t t = 0; t < tiles; t++) all[t] = t;
+            if (hip(hipMemcpy(lists, all.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy")) break;
+            uint32_t *cur = lists, *nxt = lists + tiles, *count = lists + 2 * (size_t)tiles, active = tiles;
+            while (true) {
+                const uint32_t end = std::min<uint64_t>((uint64_t)done + (uint32_t)c.batch, samples);
+                if ((rc = ptmi_scene_render_tiles(sc, samples, done, end, cur, active, seeds, b_sums, b_sq, 0, nullptr,
+                                                  err, err_len)))
+                    break;
+                if ((rc = ptmi_accumulate(sums, b_sums, n * 4, nullptr, err, err_len))) break;
+                if ((rc = ptmi_accumulate(sq, b_sq, n, nullptr, err, err_len))) break;
+                if ((rc = ptmi_error_map(sums, sq, (uint32_t)c.width, (uint32_t)c.height, se, tile_err, stats, nullptr,
+                                         err, err_len)))
+                    break;
+                if (hip(hipMemcpy(st, stats, sizeof(st), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                done = end;
+                rel = st[2] != 0.0 ? st[0] / st[2] : HUGE_VAL;
+                if (done == samples) tiles_at_max = active;
+                if ((rc = ptmi_select_tiles(tile_err, cur, active, c.noise_target * st[2], nxt, count, nullptr, err,
+                                            err_len)))
+                    break;
+                if (hip(hipMemcpy(&active, count, sizeof(active), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+                std::swap(cur, nxt);
+                if (active == 0 || done == samples) break;
+            }
+            if (rc) break;
+            if ((rc = ptmi_finalize_counts(sums, b_sums, (uint32_t)n, nullptr, err, err_len))) break;
+            if (hip(hipMemcpy(out.data(), b_sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+            counts_rgba.resize(n * 4);
+            if (hip(hipMemcpy(counts_rgba.data(), sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy"))
+                break;
+            for (size_t i = 0; i < n; i++) {
+                counts_rgba[4 * i + 0] = counts_rgba[4 * i + 1] = counts_rgba[4 * i + 2] = counts_rgba[4 * i + 3];
+                counts_rgba[4 * i + 3] = 1.0;
+            }
+            if (hip(hipMemcpy(se_host.data(), se, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+            break;
+        }
         while (done < samples) {
             const uint32_t end = std::min<uint64_t>((uint64_t)done + (uint32_t)c.batch, samples);
             if ((rc = ptmi_scene_render_moments(sc, samples, done, end, 1, 0, seeds, b_sums, b_sq, 0, nullptr, err,
@@ -159,8 +220,9 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
         if (hip(hipMemcpy(out.data(), sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
         if (hip(hipMemcpy(se_host.data(), se, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
     } while (false);
-    for (double* p : {seeds, sums, sq, b_sums, b_sq, se, stats})
+    for (double* p : {seeds, sums, sq, b_sums, b_sq, se, stats, tile_err})
         if (p) (void)hipFree(p);
+    if (lists) (void)hipFree(lists);
     ptmi_scene_destroy(sc);
     se_rgba.resize(n * 4);
     for (size_t i = 0; i < n; i++) {
@@ -225,9 +287,11 @@ int main(int argc, char** argv) {
     std::vector<double> se_rgba;
     uint32_t samples_done = (uint32_t)c.samples;
     double rel_err = 0.0;
+    std::vector<double> counts_rgba;
+    uint32_t tiles_at_max = 0;
     if (noise) {
-        rc = render_noise(c, r, textured ? &tex : nullptr, stream, out, se_rgba, samples_done, rel_err, err,
-                          sizeof(err));
+        rc = render_noise(c, r, textured ? &tex : nullptr, stream, out, se_rgba, samples_done, rel_err, counts_rgba,
+                          tiles_at_max, err, sizeof(err));
     } else if (c.gpus == 1) {
         rc = ptmi_trace(r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp, c.device_index,
                         (uint32_t)c.samples, r.camera, nullptr, stream, textured ? &tex : nullptr, out.data(), err,
@@ -262,12 +326,23 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s\n", err);
         return 1;
     }
+    if (!c.sample_map.empty() &&
+        (rc = ptmi_host_write_raw(c.sample_map.c_str(), counts_rgba.data(), c.width, c.height, err, sizeof(err)))) {
+        std::fprintf(stderr, "%s\n", err);
+        return 1;
+    }
     if (noise) std::printf("samples_done %u relative_error %.6g\n", samples_done, rel_err);
+    double traced = (double)n * samples_done;
+    if (c.adaptive) {
+        traced = 0.0;
+        for (size_t i = 0; i < n; i++) traced += counts_rgba[4 * i];
+        std::printf("adaptive mean_spp %.9g tiles_at_max %u\n", traced / (double)n, tiles_at_max);
+    }
     const double build_s = std::chrono::duration<double>(t1 - t0).count();
     const double trace_s = std::chrono::duration<double>(t2 - t1).count();
     std::fprintf(stderr, "scene %s built in %.3f s; %dx%d x %d spp traced in %.3f s (%.1f Msamples/s); wrote %s\n",
                  scene.c_str(), build_s, c.width, c.height, (int)samples_done, trace_s,
-                 (double)n * samples_done / trace_s / 1e6, png.c_str());
+                 traced / trace_s / 1e6, png.c_str());
     if (c.gpus > 1)
         std::fprintf(stderr,
                      "%d GPUs (%s split): prepare %.3f ms, render %.3f ms, combine %.3f ms, read-back %.3f ms\n",

@@ -37,7 +37,8 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_scene_size", "ptmi_scene_render", "ptmi_finalize", "ptmi_fill_seeds", "ptmi_build_info",
            "ptmi_scene_set_timing", "ptmi_scene_kernel_time", "ptmi_trace_multi", "ptmi_scene_create_textured",
            "ptmi_trace_multi_timed", "ptmi_sample_split_point", "ptmi_combine_frames",
-           "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate")
+           "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate",
+           "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts")
 
 
 class MultiTiming(ctypes.Structure):
@@ -104,6 +105,13 @@ def load_library(path=None):
         lib.ptmi_error_map.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, cp, sz]
         lib.ptmi_accumulate.restype = i32
         lib.ptmi_accumulate.argtypes = [vp, vp, sz, vp, cp, sz]
+    if hasattr(lib, "ptmi_scene_render_tiles"):  # (likewise)
+        lib.ptmi_scene_render_tiles.restype = i32
+        lib.ptmi_scene_render_tiles.argtypes = [vp, u32, u32, u32, vp, u32, vp, vp, vp, u32, vp, cp, sz]
+        lib.ptmi_select_tiles.restype = i32
+        lib.ptmi_select_tiles.argtypes = [vp, vp, u32, ctypes.c_double, vp, vp, vp, cp, sz]
+        lib.ptmi_finalize_counts.restype = i32
+        lib.ptmi_finalize_counts.argtypes = [vp, vp, u32, vp, cp, sz]
     lib.ptmi_finalize.restype = i32
     lib.ptmi_finalize.argtypes = [vp, vp, u32, u32, vp, cp, sz]
     lib.ptmi_fill_seeds.restype = i32
@@ -300,6 +308,23 @@ class Scene:
                                                  len(err))
         _check(rc, err)
 
+    def render_tiles(self, samples, sample_begin, sample_end, tiles_ptr, n_tiles, seeds_ptr, sums_ptr, sq_ptr,
+                     chunks=0, stream=0):
+        """ptmi_scene_render_tiles: render_moments() on the n_tiles 8x8 tiles whose raster indices
+        (uint32, distinct) are at tiles_ptr in device memory; every other pixel of sums_ptr and sq_ptr
+        is set to 0.  An index past the frame's tiles is skipped."""
+        err = ctypes.create_string_buffer(1024)
+        rc = self._lib.ptmi_scene_render_tiles(self._h, samples, sample_begin, sample_end,
+                                               ctypes.c_void_p(tiles_ptr or None), int(n_tiles),
+                                               ctypes.c_void_p(seeds_ptr), ctypes.c_void_p(sums_ptr),
+                                               ctypes.c_void_p(sq_ptr or None), chunks, ctypes.c_void_p(stream), err,
+                                               len(err))
+        _check(rc, err)
+
+    def finalize_counts(self, sums_ptr, out_ptr, stream=0):
+        """ptmi_finalize_counts over the scene's pixels: finalize() by each pixel's own count."""
+        finalize_counts(sums_ptr, out_ptr, self.width * self.height, stream=stream)
+
     def finalize(self, sums_ptr, out_ptr, samples, stream=0):
         err = ctypes.create_string_buffer(1024)
         rc = self._lib.ptmi_finalize(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(out_ptr),
@@ -391,3 +416,22 @@ def accumulate(dst_ptr, src_ptr, n, stream=0):
     err = ctypes.create_string_buffer(256)
     _check(load_library().ptmi_accumulate(ctypes.c_void_p(dst_ptr), ctypes.c_void_p(src_ptr), int(n),
                                           ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def select_tiles(tile_err_ptr, in_tiles_ptr, n_in, threshold, out_tiles_ptr, count_ptr, stream=0):
+    """ptmi_select_tiles: of the candidates in_tiles_ptr[0..n_in) (uint32 tile indices; 0 = the tiles
+    0..n_in themselves), those with tile_err[t] > threshold go to out_tiles_ptr in candidate order and
+    their number to count_ptr[0] (uint32).  NaN and ties are dropped, +inf is kept; the two lists must
+    not alias.  The rule is ptmi/error.py select_tiles_reference."""
+    err = ctypes.create_string_buffer(256)
+    _check(load_library().ptmi_select_tiles(ctypes.c_void_p(tile_err_ptr or None), ctypes.c_void_p(in_tiles_ptr or None),
+                                            int(n_in), float(threshold), ctypes.c_void_p(out_tiles_ptr or None),
+                                            ctypes.c_void_p(count_ptr), ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def finalize_counts(sums_ptr, out_ptr, n_pixels, stream=0):
+    """ptmi_finalize_counts: RGB = sum_c * (1.0 / n) with the pixel's own n = sums[4i+3] (0 where
+    n == 0), A = 1.0.  The rule is ptmi/error.py finalize_counts_reference."""
+    err = ctypes.create_string_buffer(256)
+    _check(load_library().ptmi_finalize_counts(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(out_ptr), int(n_pixels),
+                                               ctypes.c_void_p(stream), err, len(err)), err)

@@ -7,6 +7,10 @@ documentation and the comparator of the GPU tests.
 ``render_to_noise`` renders a frame batch by batch until its relative noise is below a target.
 Sample indices are global, so the batches [0, b), [b, 2b), ... of a ``max_samples``-spp frame are
 that frame, stopped early.
+
+``render_adaptive`` stops each 8x8 tile on its own (ptmi_scene_render_tiles, ptmi_select_tiles,
+ptmi_finalize_counts); ``select_tiles_reference`` and ``finalize_counts_reference`` restate the two
+small kernels.
 """
 import numpy as np
 
@@ -85,6 +89,31 @@ def error_map_reference(sums, sq, width, height):
     return se, tile_err, stats
 
 
+def select_tiles_reference(tile_err, in_tiles, n_in, threshold):
+    """(kept tiles as uint32, their number): of the candidates in_tiles[0..n_in) -- the tiles 0..n_in
+    themselves when in_tiles is None -- those with tile_err[t] > threshold, in candidate order.  A
+    NaN error and an error equal to the threshold are dropped, +inf is kept (ptmi_select_tiles)."""
+    err = np.asarray(tile_err, dtype=np.float64)
+    n_in = int(n_in)
+    cand = np.arange(n_in, dtype=np.uint32) if in_tiles is None else np.asarray(in_tiles, dtype=np.uint32)[:n_in]
+    with np.errstate(invalid="ignore"):
+        keep = err[cand.astype(np.int64)] > np.float64(threshold) if n_in else np.zeros(0, dtype=bool)
+    out = cand[keep]
+    return out, int(out.size)
+
+
+def finalize_counts_reference(sums):
+    """RGBA (n_pixels * 4) from frame sums (r, g, b, n per pixel) by each pixel's own count:
+    RGB = sum_c * (1.0 / n), 0 where n == 0; A = 1.0 (ptmi_finalize_counts)."""
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, 4)
+    n = s[:, 3]
+    with np.errstate(all="ignore"):
+        w = 1.0 / n
+        out = np.where((n == 0.0)[:, None], 0.0, s * w[:, None])
+    out[:, 3] = 1.0
+    return out.reshape(-1)
+
+
 def render_to_noise(scene, max_samples, batch, target, seeds_ptr, chunks=0, stream=None):
     """Render `scene` (api.Scene) until the frame's relative noise is at most `target`.
 
@@ -126,3 +155,69 @@ def render_to_noise(scene, max_samples, batch, target, seeds_ptr, chunks=0, stre
                 break
         scene.finalize(sums.data_ptr(), out.data_ptr(), done, stream=sp)
     return out, se, done, history
+
+
+def render_adaptive(scene, max_samples, batch, target, seeds_ptr, chunks=0, stream=None, keep_lists=False):
+    """Render `scene` (api.Scene) with each 8x8 tile stopping on its own noise.
+
+    Round r traces samples [r*batch, (r+1)*batch) of a `max_samples`-spp frame (the last round short
+    if needed) on the active tiles only (render_tiles), accumulates them, and takes tile_err and stats
+    from error_map over the whole frame.  A tile stays active while tile_err > threshold, with
+    threshold = target * stats[2] of that round (select_tiles, from the active list into the other of
+    two buffers, so the lists are nested and stay in raster order).  The loop ends when no tile is
+    active or the samples run out.  The active set only shrinks, so a pixel with count n holds exactly
+    samples [0, n) of the frame; the image divides each pixel by its own count (finalize_counts).
+
+    What a stopped tile is promised: its tile_err was <= the threshold of the round it stopped in.
+    The threshold follows stats[2] from round to round, so the final frame ratio stats[0] / stats[2]
+    (the last history entry) is reported, not guaranteed.  Stopping on the sample variance makes the
+    estimate slightly biased (pixels whose first samples happen to agree stop early): a property of
+    the method.  Each round waits for the device twice, for stats and for the new list's length.
+
+    `batch` >= 2 (one sample has no variance).  Returns (image, se, counts, history): float64 torch
+    tensors on the scene's device -- RGBA of W*H*4, the standard-error map and the per-pixel sample
+    counts of W*H -- and one (active tiles, threshold, stats[0] / stats[2]) per round.  With
+    keep_lists a fifth element: each round's active list, numpy uint32 arrays.
+    """
+    import torch
+    from . import api
+
+    if max_samples <= 0 or batch < 2:
+        raise ValueError("max_samples must be positive and batch at least 2")
+    w, h = scene.width, scene.height
+    npix = w * h
+    tiles = ((w + TILE - 1) // TILE) * ((h + TILE - 1) // TILE)
+    st = torch.cuda.current_stream() if stream is None else stream
+    sp = st.cuda_stream
+    with torch.cuda.stream(st):
+        kw = dict(dtype=torch.float64, device="cuda")
+        sums, sq = torch.zeros(npix * 4, **kw), torch.zeros(npix, **kw)
+        b_sums, b_sq = torch.empty(npix * 4, **kw), torch.empty(npix, **kw)
+        se, stats, out = torch.empty(npix, **kw), torch.empty(4, **kw), torch.empty(npix * 4, **kw)
+        tile_err = torch.empty(tiles, **kw)
+        cur = torch.arange(tiles, dtype=torch.int32, device="cuda")  # (uint32 on the device side)
+        nxt, count = torch.empty_like(cur), torch.zeros(1, dtype=torch.int32, device="cuda")
+        history, lists, done, active = [], [], 0, tiles
+        while True:
+            end = min(done + batch, max_samples)
+            if keep_lists:
+                lists.append(cur[:active].cpu().numpy().astype(np.uint32))
+            scene.render_tiles(max_samples, done, end, cur.data_ptr(), active, seeds_ptr, b_sums.data_ptr(),
+                               b_sq.data_ptr(), chunks=chunks, stream=sp)
+            api.accumulate(sums.data_ptr(), b_sums.data_ptr(), npix * 4, stream=sp)
+            api.accumulate(sq.data_ptr(), b_sq.data_ptr(), npix, stream=sp)
+            api.error_map(sums.data_ptr(), sq.data_ptr(), w, h, stats.data_ptr(), se_ptr=se.data_ptr(),
+                          tile_err_ptr=tile_err.data_ptr(), stream=sp)
+            done = end
+            rms, _, mean, _ = stats.tolist()  # (waits for the round)
+            threshold = target * mean
+            history.append((active, threshold, rms / mean if mean != 0.0 else float("inf")))
+            api.select_tiles(tile_err.data_ptr(), cur.data_ptr(), active, threshold, nxt.data_ptr(),
+                             count.data_ptr(), stream=sp)
+            active = int(count.item())  # (waits for the list)
+            cur, nxt = nxt, cur
+            if active == 0 or done == max_samples:
+                break
+        counts = sums[3::4].clone()
+        scene.finalize_counts(sums.data_ptr(), out.data_ptr(), stream=sp)
+    return (out, se, counts, history, lists) if keep_lists else (out, se, counts, history)
