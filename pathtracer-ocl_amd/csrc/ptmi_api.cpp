@@ -47,6 +47,7 @@ hipError_t launch_select_tiles(const double* tile_err, const uint32_t* in_tiles,
                                uint32_t* out_tiles, uint32_t* count, hipStream_t st);
 hipError_t launch_seeds(double* seeds, uint32_t n, uint64_t stream, hipStream_t st);
 hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st);
+hipError_t launch_camera_terms(const DevScene& S, hipStream_t st);
 hipError_t launch_hemi_table(double* out, int* mismatch, hipStream_t st);
 hipError_t launch_combine(const double* parts, uint32_t nparts, size_t npix, double* out, uint32_t samples,
                           hipStream_t st);
@@ -701,9 +702,13 @@ int upload_scene(const HostScene& hs, int device_index, const ptmi_textures* tex
     s->dev.n_tri = hs.n_tri;
     s->dev.cam = hs.cam;
     {  // the camera record in device memory (ptmi_kernels.hip camera_ptr)
-        SCENE_TRY(hipMalloc(&s->buffers[14], sizeof(DevCamera)));
+        // and, behind it, the camera terms of this scene's planes and spheres (ptmi_device.h), computed
+        // from the record just uploaded: they go with every upload of the camera record
+        SCENE_TRY(hipMalloc(&s->buffers[14], cam_record_bytes(s->dev.n_planes, s->dev.n_spheres_st)));
         SCENE_TRY(hipMemcpy(s->buffers[14], &hs.cam, sizeof(DevCamera), hipMemcpyHostToDevice));
         s->dev.camg = (const DevCamera*)s->buffers[14];
+        SCENE_TRY(launch_camera_terms(s->dev, nullptr));
+        SCENE_TRY(hipDeviceSynchronize());
     }
     SCENE_TRY(resident_waves(s));
 #undef SCENE_TRY

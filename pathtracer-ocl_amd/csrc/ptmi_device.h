@@ -179,6 +179,19 @@ struct DevScene {
     const double* hemi;  // randomVectorInHemisphere table, 2^16 x 4 doubles (hemi_table_kernel)
 };
 
+// The camera terms: the origin half of a camera ray's intersections (ray origin = cam.origin, no DoF),
+// computed on the device with find_closest_prims' own expressions whenever the camera record is uploaded
+// (ptmi_kernels.hip camera_terms_pass, cam_term) and read by the lockstep loop's first bounce.  They
+// belong to the camera, so they live behind its record in the same allocation (DevScene::camg) and the
+// by-value DevScene -- every kernel's argument layout -- stays as it is:
+//   cam_planes  [n_planes]         indexed like DevScene::planes: the origin term of the plane's row-1 sum
+//   cam_spheres [n_spheres_st][4]  indexed like DevScene::spheres: M origin + t (x, y, z), c = |.|^2 - 1
+constexpr int kCamSphere = 4;
+inline size_t cam_record_bytes(int32_t n_planes, int32_t n_spheres_st) {
+    return sizeof(DevCamera) + ((size_t)n_planes + (size_t)kCamSphere * (size_t)n_spheres_st) * sizeof(double);
+}
+static_assert(sizeof(DevCamera) % sizeof(double) == 0, "the terms follow the record as doubles");
+
 // One BVH walk of a ray (walk_kernel / walk_pool_kernel): the world-space ray and the
 // best primitive hit so far (t, pk as Hit::pk), one 64-B line; and its result, the
 // closest hit over the primitives and every group object (tri / ti -1 when no triangle

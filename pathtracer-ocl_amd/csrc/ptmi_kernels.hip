@@ -148,6 +148,17 @@ __device__ WalkRes* ptmi_cap_res;
 __device__ unsigned ptmi_cap_n, ptmi_cap_max;
 #endif
 
+// The lockstep loop (trace_lockstep), both in the product; 0 restores the earlier form for A/B builds
+// (tools/build_variant.sh; same images either way, tests/test_gpu_stages.py):
+#ifndef PTMI_STAGES
+#define PTMI_STAGES 1  // the bounce loop staged by its wave-uniform bounce index: the camera ray's bounce, the
+                       // middle bounces, the last record (0: one loop over b)
+#endif
+#ifndef PTMI_CAM_TERMS
+#define PTMI_CAM_TERMS 1  // kernels without DoF: the camera ray's bounce reads the origin half of every plane /
+                          // sphere intersection from the scene's camera terms (ptmi_device.h; needs PTMI_STAGES)
+#endif
+
 static constexpr unsigned kMaxEffectiveBounces = 4;  // tracer.cl:2
 static constexpr unsigned kMaxBounces = 10;          // tracer.cl:3
 static constexpr double kEps = 0.0001;               // tracer.cl:4
@@ -1110,13 +1121,31 @@ __device__ __forceinline__ void consider_sel(Hit& h, double t, int obj, int key)
     consider_pk(h, t, pack_hit(obj, key));
 }
 
+// A term of find_closest_prims that depends on the ray's origin only, formed by f().  CAM says where it
+// comes from: 0 -- computed in place; 1 -- the ray starts at DevCamera::origin and the term is read from
+// the scene's table (ptmi_device.h cam_planes / cam_spheres; a uniform index: a scalar load); 2 -- computed
+// in place and written to the table (camera_terms_pass: origin = the camera's, once per scene).  So a
+// table entry is the value the same expression gives in the same function, not a restatement of it.
+template <int CAM, typename F>
+__device__ __forceinline__ double cam_term(const double* tab, int i, F&& f) {
+    if constexpr (CAM == 1) {
+        return cmem(tab)[i];
+    } else {
+        const double v = f();
+        if constexpr (CAM == 2) const_cast<double*>(tab)[i] = v;
+        return v;
+    }
+}
+
 // intersectSphere (tracer.cl:448-476) on an object-space ray: the quadratic ...
-template <bool A>
-__device__ __forceinline__ void sphere_quad(d4 o, d4 d, double& a, double& b, double& disc) {
+// (CAM, ct: cam_term for c, the one origin-only term; vtc itself is then a table value already.)
+template <bool A, int CAM = 0>
+__device__ __forceinline__ void sphere_quad(d4 o, d4 d, double& a, double& b, double& disc,
+                                            const double* ct = nullptr) {
     d4 vtc = mk(o.x - 0.0, o.y - 0.0, o.z - 0.0, A ? 0.0 : o.w - 1.0);
     a = dotv<A>(d, d);
     b = 2.0 * dotv<A>(d, vtc);
-    double c = dotv<A>(vtc, vtc) - 1.0;
+    double c = cam_term<CAM>(ct, 3, [&] { return dotv<A>(vtc, vtc) - 1.0; });
     disc = (b * b) - 4 * a * c;
 }
 // ... and its roots.
@@ -1172,8 +1201,9 @@ __device__ __forceinline__ void sphere_test(Hit& h, d4 o, d4 d, int slot, int ke
 // reference's order, give oy and dy bit for bit up to the sign of an exact zero, which
 // neither t = -oy / dy nor its tests observe (t is then +-0, or |dy| is below EPSILON).
 // The walls of the reference scenes have one or two such zeros.
-template <int NZ, typename M>
-__device__ __forceinline__ void plane_rows_nz(M m, d4 ro, d4 rd, double& oy, double& dy) {
+template <int NZ, int CAM = 0, typename M>
+__device__ __forceinline__ void plane_rows_nz(M m, d4 ro, d4 rd, double& oy, double& dy, const double* ct = nullptr,
+                                              int pi = 0) {
     static_assert(NZ >= 1 && NZ <= 7, "at least one live term");
     double o = 0.0, d = 0.0;
     bool any = false;
@@ -1185,16 +1215,24 @@ __device__ __forceinline__ void plane_rows_nz(M m, d4 ro, d4 rd, double& oy, dou
     if constexpr ((NZ & 1) != 0) term(m[0], ro.x, rd.x);
     if constexpr ((NZ & 2) != 0) term(m[1], ro.y, rd.y);
     if constexpr ((NZ & 4) != 0) term(m[2], ro.z, rd.z);
-    oy = o + m[3];
+    oy = cam_term<CAM>(ct, pi, [&] { return o + m[3]; });
     dy = d;
 }
 
 // findClosestIntersection (tracer.cl:537-742), one loop per object type.  Loop
 // indices are wave-uniform, so object data arrives through scalar loads.
-template <int FL>
+// CAM (cam_term): 1 -- ro is the scene camera's origin (the lockstep loop's first bounce without DoF):
+// the origin terms of the planes and the scale+translate spheres come from the scene's tables and only
+// the direction half is computed; everything from plane_q / sphere_quad's a, b, disc on is the same code.
+template <int FL, int CAM = 0>
 __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 rd) {
     constexpr bool A = !(FL & F_PROJ);
+    static_assert(CAM == 0 || A, "camera terms: affine kernels");
     Hit h{1024.0, -1, -1, -1, 0.0, 0.0};
+    // the camera terms behind the camera record (ptmi_device.h): cam_planes, cam_spheres
+    [[maybe_unused]] const double* const cpl = CAM ? (const double*)(S.camg + 1) : nullptr;
+    [[maybe_unused]] const double* const csp = CAM ? cpl + S.n_planes : nullptr;
+    auto pterm = [&](int i, auto&& f) { return cam_term<CAM>(cpl, i, f); };
     // Plane and sphere records are scalar loads; the next object's record is loaded
     // while the current one is intersected (its latency is otherwise exposed on
     // every object).  Duplicate-free: the last iteration re-loads its own record.
@@ -1204,9 +1242,9 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
     // intersectPlane (478-483): row 1 only.  Planes are taken two at a time so the
     // two independent division chains overlap (then one odd plane).
     // Row 1 of mul() for the plane's origin and direction (intersectPlane, 478-483).
-    auto plane_rows = [&](const auto& P, double& oy, double& dy) {
+    auto plane_rows = [&](const auto& P, double& oy, double& dy, int pi) {
         const auto* m = P.row1;
-        oy = ((m[0] * ro.x + m[1] * ro.y) + m[2] * ro.z) + (A ? m[3] : m[3] * ro.w);
+        oy = pterm(pi, [&] { return ((m[0] * ro.x + m[1] * ro.y) + m[2] * ro.z) + (A ? m[3] : m[3] * ro.w); });
         const double dy0 = (m[0] * rd.x + m[1] * rd.y) + m[2] * rd.z;
         dy = A ? dy0 : dy0 + m[3] * rd.w;
     };
@@ -1228,9 +1266,9 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         k0 = big & (q0 > kEps);
         k1 = big & (q1 > kEps);
     };
-    auto plane_t = [&](const auto& P, double& q, bool& ok) {
+    auto plane_t = [&](const auto& P, double& q, bool& ok, int pi) {
         double oy, dy;
-        plane_rows(P, oy, dy);
+        plane_rows(P, oy, dy, pi);
         plane_q(oy, dy, q, ok);
     };
     auto plane_take = [&](const auto& P, double q, bool ok) {
@@ -1251,14 +1289,14 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
             double oy0, dy0, oy1, dy1, q0, q1;
             bool k0, k1;
             if (P0.par) {  // parallel pair: one product m1 y, one direction term, one reciprocal
-                const double a = P0.row1[1] * ro.y;
-                oy0 = a + P0.row1[3];
-                oy1 = a + P1.row1[3];
+                [[maybe_unused]] const double a = P0.row1[1] * ro.y;
+                oy0 = pterm(p, [&] { return a + P0.row1[3]; });
+                oy1 = pterm(p + 1, [&] { return a + P1.row1[3]; });
                 dy0 = P0.row1[1] * rd.y;
                 plane_q2(oy0, oy1, dy0, q0, k0, q1, k1);
             } else {
-                plane_rows_nz<2>(P0.row1, ro, rd, oy0, dy0);
-                plane_rows_nz<2>(P1.row1, ro, rd, oy1, dy1);
+                plane_rows_nz<2, CAM>(P0.row1, ro, rd, oy0, dy0, cpl, p);
+                plane_rows_nz<2, CAM>(P1.row1, ro, rd, oy1, dy1, cpl, p + 1);
                 plane_q(oy0, dy0, q0, k0);
                 plane_q(oy1, dy1, q1, k1);
             }
@@ -1285,11 +1323,13 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         if constexpr ((NZ & 4) != 0) o = any ? o + m[2] * z : m[2] * z;
         return o;
     };
-    auto par_pair = [&](auto nzc, const auto& P0, const auto& P1, double& q0, bool& k0, double& q1, bool& k1) {
+    auto par_pair = [&](auto nzc, const auto& P0, const auto& P1, double& q0, bool& k0, double& q1, bool& k1,
+                        int pi) {
         const auto* m = P0.row1;
-        const double a = sum_nz(nzc, m, ro.x, ro.y, ro.z);
+        [[maybe_unused]] const double a = sum_nz(nzc, m, ro.x, ro.y, ro.z);
         const double dy = sum_nz(nzc, m, rd.x, rd.y, rd.z);
-        plane_q2(a + m[3], a + P1.row1[3], dy, q0, k0, q1, k1);
+        plane_q2(pterm(pi, [&] { return a + m[3]; }), pterm(pi + 1, [&] { return a + P1.row1[3]; }), dy, q0, k0, q1,
+                 k1);
     };
     for (; p + 1 < np; p += 2) {
         PTMI_WADD(48, 1ull);
@@ -1298,21 +1338,21 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         bool k0, k1;
         if (A && P0.par && PTMI_R6_PLNZ) {
             switch (P0.nz) {
-                case 3: par_pair(std::integral_constant<int, 3>(), P0, P1, q0, k0, q1, k1); break;
-                case 5: par_pair(std::integral_constant<int, 5>(), P0, P1, q0, k0, q1, k1); break;
-                case 6: par_pair(std::integral_constant<int, 6>(), P0, P1, q0, k0, q1, k1); break;
-                default: par_pair(std::integral_constant<int, 7>(), P0, P1, q0, k0, q1, k1); break;
+                case 3: par_pair(std::integral_constant<int, 3>(), P0, P1, q0, k0, q1, k1, p); break;
+                case 5: par_pair(std::integral_constant<int, 5>(), P0, P1, q0, k0, q1, k1, p); break;
+                case 6: par_pair(std::integral_constant<int, 6>(), P0, P1, q0, k0, q1, k1, p); break;
+                default: par_pair(std::integral_constant<int, 7>(), P0, P1, q0, k0, q1, k1, p); break;
             }
         } else if (A && P0.par) {  // parallel pair: one sum of the origin's x, y, z terms, one direction term
             const auto* m = P0.row1;  // and one reciprocal (row1[0..2] of P1 are the same bits)
-            const double a = (m[0] * ro.x + m[1] * ro.y) + m[2] * ro.z;
-            oy0 = a + m[3];
-            oy1 = a + P1.row1[3];
+            [[maybe_unused]] const double a = (m[0] * ro.x + m[1] * ro.y) + m[2] * ro.z;
+            oy0 = pterm(p, [&] { return a + m[3]; });
+            oy1 = pterm(p + 1, [&] { return a + P1.row1[3]; });
             dy0 = (m[0] * rd.x + m[1] * rd.y) + m[2] * rd.z;
             plane_q2(oy0, oy1, dy0, q0, k0, q1, k1);
         } else {
-            plane_rows(P0, oy0, dy0);
-            plane_rows(P1, oy1, dy1);
+            plane_rows(P0, oy0, dy0, p);
+            plane_rows(P1, oy1, dy1, p + 1);
             plane_q(oy0, dy0, q0, k0);
             plane_q(oy1, dy1, q1, k1);
         }
@@ -1327,21 +1367,31 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         if (A && PTMI_R6_PLNZ) {
             double oy, dy;
             switch (P0.nz) {
-                case 3: plane_rows_nz<3>(P0.row1, ro, rd, oy, dy); break;
-                case 5: plane_rows_nz<5>(P0.row1, ro, rd, oy, dy); break;
-                case 6: plane_rows_nz<6>(P0.row1, ro, rd, oy, dy); break;
-                default: plane_rows(P0, oy, dy); break;
+                case 3: plane_rows_nz<3, CAM>(P0.row1, ro, rd, oy, dy, cpl, p); break;
+                case 5: plane_rows_nz<5, CAM>(P0.row1, ro, rd, oy, dy, cpl, p); break;
+                case 6: plane_rows_nz<6, CAM>(P0.row1, ro, rd, oy, dy, cpl, p); break;
+                default: plane_rows(P0, oy, dy, p); break;
             }
             plane_q(oy, dy, q0, k0);
         } else {
-            plane_t(P0, q0, k0);
+            plane_t(P0, q0, k0, p);
         }
         plane_take(P0, q0, k0);
     }
     const int nq = (PTMI_ABLATE & 16) ? 0 : S.n_spheres_st;
-    auto sphere_ray = [&](const auto& Q, d4& o, d4& d) {
+    auto sphere_ray = [&](const auto& Q, d4& o, d4& d, [[maybe_unused]] const double* ct) {
         if constexpr (A) {
-            o = mk(Q.m0 * ro.x + Q.m3, Q.m5 * ro.y + Q.m7, Q.m10 * ro.z + Q.m11, 1.0);
+            if constexpr (CAM == 1) {
+                o = mk(cmem(ct)[0], cmem(ct)[1], cmem(ct)[2], 1.0);
+            } else {
+                o = mk(Q.m0 * ro.x + Q.m3, Q.m5 * ro.y + Q.m7, Q.m10 * ro.z + Q.m11, 1.0);
+                if constexpr (CAM == 2) {
+                    double* w = const_cast<double*>(ct);
+                    w[0] = o.x;
+                    w[1] = o.y;
+                    w[2] = o.z;
+                }
+            }
             d = mk(Q.m0 * rd.x, Q.m5 * rd.y, Q.m10 * rd.z, 0.0);
         } else {
             o = mk(Q.m0 * ro.x + Q.m3 * ro.w, Q.m5 * ro.y + Q.m7 * ro.w, Q.m10 * ro.z + Q.m11 * ro.w, Q.m15 * ro.w);
@@ -1385,9 +1435,9 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
     if (PTMI_R6_SPH && nq == 1) {
         const auto& Q0 = cmem(S.spheres)[0];
         d4 o0, d0;
-        sphere_ray(Q0, o0, d0);
+        sphere_ray(Q0, o0, d0, csp + kCamSphere * q);
         double a0, b0, disc0;
-        sphere_quad<A>(o0, d0, a0, b0, disc0);
+        sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * q);
         first(a0, b0, disc0, Q0.slot, Q0.key);
         q = 1;
     }
@@ -1395,11 +1445,11 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         PTMI_WADD(50, 1ull);
         const auto &Q0 = cmem(S.spheres)[0], &Q1 = cmem(S.spheres)[1];
         d4 o0, d0, o1, d1;
-        sphere_ray(Q0, o0, d0);
-        sphere_ray(Q1, o1, d1);
+        sphere_ray(Q0, o0, d0, csp + kCamSphere * q);
+        sphere_ray(Q1, o1, d1, csp + kCamSphere * (q + 1));
         double a0, b0, disc0, a1, b1, disc1;
-        sphere_quad<A>(o0, d0, a0, b0, disc0);
-        sphere_quad<A>(o1, d1, a1, b1, disc1);
+        sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * q);
+        sphere_quad<A, CAM>(o1, d1, a1, b1, disc1, csp + kCamSphere * (q + 1));
         first(a0, b0, disc0, Q0.slot, Q0.key);
         defer(a1, b1, disc1, Q1.slot, Q1.key);
         q = 2;
@@ -1408,11 +1458,11 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         PTMI_WADD(51, 1ull);
         const auto &Q0 = cmem(S.spheres)[q], &Q1 = cmem(S.spheres)[q + 1];
         d4 o0, d0, o1, d1;
-        sphere_ray(Q0, o0, d0);
-        sphere_ray(Q1, o1, d1);
+        sphere_ray(Q0, o0, d0, csp + kCamSphere * q);
+        sphere_ray(Q1, o1, d1, csp + kCamSphere * (q + 1));
         double a0, b0, disc0, a1, b1, disc1;
-        sphere_quad<A>(o0, d0, a0, b0, disc0);
-        sphere_quad<A>(o1, d1, a1, b1, disc1);
+        sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * q);
+        sphere_quad<A, CAM>(o1, d1, a1, b1, disc1, csp + kCamSphere * (q + 1));
         defer(a0, b0, disc0, Q0.slot, Q0.key);
         defer(a1, b1, disc1, Q1.slot, Q1.key);
     }
@@ -1420,9 +1470,9 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         PTMI_WADD(52, 1ull);
         const auto& Q0 = cmem(S.spheres)[q];
         d4 o0, d0;
-        sphere_ray(Q0, o0, d0);
+        sphere_ray(Q0, o0, d0, csp + kCamSphere * q);
         double a0, b0, disc0;
-        sphere_quad<A>(o0, d0, a0, b0, disc0);
+        sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * q);
         defer(a0, b0, disc0, Q0.slot, Q0.key);  // (q >= 2 here when PTMI_R6_SPH: the first sphere is peeled)
     }
     if (pend) {
@@ -2193,9 +2243,11 @@ __device__ __forceinline__ bool bounce_shade(const DevScene& S, PathState& P, co
                       // 167.9, C3 179.5 -> 174.9 ms); 7 waves (72 VGPRs, 96 B/lane) lose 10 %
 #endif
 #ifndef PTMI_WAVES_LOCKSTEP_DOF
-#define PTMI_WAVES_LOCKSTEP_DOF 6  // ... the lockstep loop with DoF: at 72 VGPRs it spills 48 B/lane of per-sample
-                                   // values; same box, 2048 spp: C3 130.1 ms at 7 waves, 124.7 at 6 (C2, no DoF,
-                                   // prefers 7: 120.0 against 121.1 ms; profiles/lockstep/SUMMARY.md)
+#define PTMI_WAVES_LOCKSTEP_DOF 7  // ... the lockstep loop with DoF.  Staged (PTMI_STAGES) it needs 75 VGPRs without
+                                   // scratch, and 7 waves win: same box, 2048 spp, C3 114.0-114.5 ms at 7 waves,
+                                   // 118.1-118.3 at 6 (C2, no DoF: 110.4-110.7 at 7, 114.9-115.3 at 6;
+                                   // profiles/stages/SUMMARY.md).  The single loop spilled 48 B/lane at 72 VGPRs
+                                   // and took 6: C3 130.1 ms at 7 waves, 124.7 at 6 (profiles/lockstep/SUMMARY.md)
 #endif
 #ifndef PTMI_WAVES_MATERIALS
 #define PTMI_WAVES_MATERIALS 5 // ... with reflective / refractive materials: ~95-101 VGPRs since round 3 (LDS colour
@@ -3038,6 +3090,64 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
             if constexpr ((FL & F_XRNG) != 0) P.rng = xseed(seed_bits, n);
         }
         PTMI_TADD(12, t_a);
+#if PTMI_STAGES
+        // One bounce of the wave's live lanes at the wave-uniform index b.  kind: 0 -- the camera ray
+        // (b == 0 at compile time; without DoF its origin terms come from the scene's tables), 1 -- a
+        // middle bounce, 2 -- the last record: bounce_tail alone, no path state written.
+        // A lane whose path has ended, or that has none, never reads its path state again (start_path
+        // rewrites all of it), but the compiler sees the old values flow round the shading block to the
+        // next stage and keeps them apart from the new ones: a copy of ro, rd and the mask into other
+        // registers and back, per stage.  On those paths the state is therefore redefined by an empty asm
+        // -- no instruction; the value is whatever the register holds -- so the new state has one home,
+        // written under the exec mask of the lanes that go on.
+        auto forget = [](auto& v) { asm volatile("" : "=v"(v)); };
+        auto forget_path = [&] {
+            forget(P.ro.x), forget(P.ro.y), forget(P.ro.z);
+            forget(P.rd.x), forget(P.rd.y), forget(P.rd.z);
+            forget(P.mr), forget(P.mg), forget(P.mb);
+            if constexpr ((FL & F_XRNG) != 0) forget(P.rng.s0), forget(P.rng.s1), forget(P.rng.s2), forget(P.rng.s3);
+        };
+        auto bounce = [&](auto kind, const uint32_t b) {
+            constexpr int K = decltype(kind)::value;
+            constexpr int CAM = (K == 0 && !kDof && PTMI_CAM_TERMS) ? 1 : 0;
+            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
+            if (alive) {
+                PTMI_TSTAMP(t_b);
+                PTMI_WADD(45, 1ull);
+                PTMI_WADD(46, (unsigned long long)__popcll(__ballot(1)));
+                Hit h;
+                if (P.dead) h.pk = -1;
+                else h = find_closest_prims<FL, CAM>(S, P.ro, P.rd);
+                PTMI_TADD(13, t_b);
+                PTMI_TSTAMP(t_d);
+                // b is the path's bounce index and its effectiveBounces, for every lane alike.
+                P.b = P.effective = b;
+                bool ended = true;
+                if constexpr (K == 2) bounce_tail(S, P, h, b, acm);
+                else ended = bounce_shade<FL, true, false, true>(S, P, h, fgi, n, acm);
+                if (ended) {
+                    acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
+                    acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
+                    acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+                    // (F_MOM) bounce_tail's and bounce_shade's paths end in the same add
+                    if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
+                    alive = false;
+                    if constexpr (K != 2) forget_path();
+                }
+                PTMI_TADD(15, t_d);
+            } else if constexpr (K != 2) {
+                forget_path();
+            }
+            PTMI_WADD(10, 1ull);
+        };
+        constexpr uint32_t kLast = (kMaxBounces < kMaxEffectiveBounces ? kMaxBounces : kMaxEffectiveBounces) - 1;
+        static_assert(kLast >= 1, "the camera ray's bounce is not the last record");
+        if (__any(alive)) bounce(std::integral_constant<int, 0>(), 0u);
+#pragma unroll 1  // the middle bounces stay a loop: the smaller code (profiles/stages/SUMMARY.md)
+        for (uint32_t b = 1; b < kLast && __any(alive); b++) bounce(std::integral_constant<int, 1>(), b);
+        if (__any(alive)) bounce(std::integral_constant<int, 2>(), kLast);
+    }
+#else
         for (uint32_t b = 0; __any(alive); b++) {
             const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
             if (alive) {
@@ -3069,6 +3179,7 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
             PTMI_WADD(10, 1ull);
         }
     }
+#endif
     PTMI_TADD(16, t_loop);
 #if PTMI_STATS
     if (PTMI_FIRST_ACTIVE())
@@ -3853,6 +3964,20 @@ hipError_t launch_hemi_table(double* out, int* mismatch, hipStream_t st) {
 
 hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st) {
     hipLaunchKernelGGL(plane_normals_kernel, dim3(1), dim3(64), 0, st, objs, n);
+    return hipGetLastError();
+}
+
+// The scene's camera terms (ptmi_device.h, behind the camera record S.camg): one lane runs
+// find_closest_prims on a ray from the uploaded record's origin in its recording form (cam_term, CAM 2),
+// which writes each origin-only term where the function forms it.  The direction and the hit are not used.
+__global__ void camera_terms_pass(DevScene S) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double* co = S.camg->origin;
+    (void)find_closest_prims<0, 2>(S, mk(co[0], co[1], co[2], 1.0), mk(0.0, 0.0, -1.0, 0.0));
+}
+
+hipError_t launch_camera_terms(const DevScene& S, hipStream_t st) {
+    hipLaunchKernelGGL(camera_terms_pass, dim3(1), dim3(64), 0, st, S);
     return hipGetLastError();
 }
 
