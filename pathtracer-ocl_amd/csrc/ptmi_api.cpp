@@ -1191,7 +1191,7 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
     const bool partial_frame = tile_stride > 1 || list_dev;  // un-owned tiles
     if (partial_frame) HIP_TRY(hipMemsetAsync(sums_dev, 0, (size_t)npix * 4 * sizeof(double), st));
     if (partial_frame && sq_dev) HIP_TRY(hipMemsetAsync(sq_dev, 0, (size_t)npix * sizeof(double), st));
-    const bool planes = (s->flags & 1) == 0 || (PTMI_MESH_PLANES && !split);  // partial layout (ptmi_kernels.hip store_sums)
+    const bool planes = (s->flags & 1) == 0 || !split;  // partial layout (ptmi_kernels.hip store_sums)
     // (moment renders: one more plane of partials, ptmi_kernels.hip store_mom)
     const size_t need = (size_t)wp.n_tail * 64 * chunks * ((planes ? 3 : 4) + (sq_dev ? 1 : 0)) * sizeof(double);
     if (need > s->partial_bytes) {

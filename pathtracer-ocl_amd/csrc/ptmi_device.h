@@ -140,7 +140,7 @@ struct alignas(16) PlaneRec {  // intersectPlane needs row 1 of the inverse only
     double row1[4];
     int32_t slot, key;  // DevScene::objs slot, reference list index
     int32_t par;        // affine pairing (find_closest_prims): the next plane has the same row1[0..2]
-    int32_t nz;         // bit i set: row1[i] (i < 3) is not +-0 (the affine kernels skip +-0 terms)
+    int32_t nz;         // bit i set: row1[i] (i < 3) is not +-0 (no kernel reads it; the record keeps its layout)
 };
 struct alignas(16) SphereRec {  // sphere with the scale+translate inverse pattern
     double m0, m3, m5, m7, m10, m11, m15, pad;
@@ -243,19 +243,13 @@ constexpr uint32_t kSlotFree = 0xFFFFFFFFu, kSlotDead = 0xFFFFFFFEu;
 
 constexpr int kTile = 8;          // a wave64 covers an 8x8 pixel tile
 
-// Chunk partials of the mesh kernels as r, g, b planes, as the kernels without meshes store
-// them, instead of (r, g, b, samples) records (ptmi_kernels.hip store_sums; round 6).
-#ifndef PTMI_MESH_PLANES
-#define PTMI_MESH_PLANES 1
-#endif
-
 // One launch's work items (trace_kernel, by value).  The owned tiles are
 // tile_offset + k * tile_stride, k = 0, 1, ... (or tiles[k], see below)  The first n_whole of them are one
 // item each over the whole sample range [s_begin, s_end), summed straight into the
 // frame; the last n_tail are split into nchunks sample chunks of chunk_len, one
 // item each, whose sums go to a partial buffer (chunk-major: chunk c of tail tile tt,
-// lane l at slot (c * n_tail + tt) * 64 + l of three planes r, g, b, or, in the mesh
-// kernels, as one (r, g, b, samples) record per slot) that reduce_chunks_kernel adds
+// lane l at slot (c * n_tail + tt) * 64 + l of three planes r, g, b; the study build's split
+// form keeps one (r, g, b, samples) record per slot) that reduce_chunks_kernel adds
 // up in chunk order.  Items are numbered whole tiles first, so the short chunk items
 // fill the end of the launch.
 struct WorkPlan {

@@ -100,39 +100,11 @@ __shared__ unsigned long long ptmi_wstat[1][64];
 #define PTMI_STUDY 0
 #endif
 
-// Round-6 instruction cuts of the bounce loop (each a switch, measured one by one on the GPU;
-// profiles/r6/SUMMARY.md).  Every one leaves the images bit-identical.
-#ifndef PTMI_R6_LOOP
-#define PTMI_R6_LOOP 1  // the hit scoped to the active block (no loop-carried copies)
-#endif
-#ifndef PTMI_R6_SPH
-#define PTMI_R6_SPH 1  // deferred sphere roots: first sphere taken without selects, (slot, key) packed
-#endif
-#ifndef PTMI_R6_SLOT
-#define PTMI_R6_SLOT 1  // hemisphere-table slot test: one conversion pair, no range test
-#endif
-#ifndef PTMI_R6_PLNZ
-#define PTMI_R6_PLNZ 0  // affine planes past the floor / ceiling run: +-0 row entries skipped by pattern
-                        // (measured slower: C2 +0.8 %, C3 +2.3 %, profiles/r6/SUMMARY.md)
-#endif
-#ifndef PTMI_R6_VACC
-#define PTMI_R6_VACC 1  // the per-pixel colour sums really in LDS (volatile slots), not promoted to VGPRs
-#endif
-#ifndef PTMI_R6_FRACT
-#define PTMI_R6_FRACT 1  // noise fract as v_fract_f32 (exhaustively checked equal to ocml's fract)
-#endif
+// The one round-6 instruction cut still behind a switch (the settled ones: DESIGN.md "settled switches").
 #ifndef PTMI_R6_NPAIR
 #define PTMI_R6_NPAIR 0  // the two draws of a noise3D pair evaluated together (ptmi_sinf.h noise_sinf2):
                          // 1 both sites, 2 camera only, 3 hemisphere only.  Measured slower, C2 +0.6 / +0.3 /
                          // +0.5 % (its two interleaved chains hold more registers at the peak)
-#endif
-
-// The lockstep item loop of the all-diffuse kernels without meshes (trace_kernel, kLockstepOf): a wave
-// runs its 64 pixels' sample n together, so the bounce index is wave-uniform and a path's last bounce
-// runs the emission step alone (DESIGN.md s2 "a path's dead tail").  0: the regeneration loop with the
-// camera buffer and the full shading on every bounce, for A/B builds (tools/build_variant.sh).  Same images.
-#ifndef PTMI_LOCKSTEP
-#define PTMI_LOCKSTEP 1
 #endif
 
 namespace ptmi {
@@ -146,17 +118,6 @@ __device__ unsigned ptmi_tl_max;
 __device__ WalkReq* ptmi_cap_req;
 __device__ WalkRes* ptmi_cap_res;
 __device__ unsigned ptmi_cap_n, ptmi_cap_max;
-#endif
-
-// The lockstep loop (trace_lockstep), both in the product; 0 restores the earlier form for A/B builds
-// (tools/build_variant.sh; same images either way, tests/test_gpu_stages.py):
-#ifndef PTMI_STAGES
-#define PTMI_STAGES 1  // the bounce loop staged by its wave-uniform bounce index: the camera ray's bounce, the
-                       // middle bounces, the last record (0: one loop over b)
-#endif
-#ifndef PTMI_CAM_TERMS
-#define PTMI_CAM_TERMS 1  // kernels without DoF: the camera ray's bounce reads the origin half of every plane /
-                          // sphere intersection from the scene's camera terms (ptmi_device.h; needs PTMI_STAGES)
 #endif
 
 static constexpr unsigned kMaxEffectiveBounces = 4;  // tracer.cl:2
@@ -365,8 +326,7 @@ __device__ __forceinline__ float noise3d(float x, float y, float z) {
     float v = sn * 43758.5453f;
     // ocml's fract: min(v - floor(v), 0x1.fffffep-1).  v_fract_f32 returns the same bits for every
     // finite float (tests/test_gpu_rng.py, exhaustive on the GPU), in one instruction instead of three.
-    if (PTMI_R6_FRACT) return __builtin_amdgcn_fractf(v);
-    return fminf(v - floorf(v), 0x1.fffffep-1f);
+    return __builtin_amdgcn_fractf(v);
 }
 
 // Two noise3D draws at once (the camera's offsets, the hemisphere's uniforms): each draw's
@@ -391,8 +351,8 @@ __device__ __forceinline__ void noise3d_pair(float x1, float y1, float z1, float
     float sn1, sn2;
     noise_sinf2(s1, s2, [](float v) { return sinf_ocml(v); }, sn1, sn2);
     const float v1 = sn1 * 43758.5453f, v2 = sn2 * 43758.5453f;
-    u1 = PTMI_R6_FRACT ? __builtin_amdgcn_fractf(v1) : fminf(v1 - floorf(v1), 0x1.fffffep-1f);
-    u2 = PTMI_R6_FRACT ? __builtin_amdgcn_fractf(v2) : fminf(v2 - floorf(v2), 0x1.fffffep-1f);
+    u1 = __builtin_amdgcn_fractf(v1);
+    u2 = __builtin_amdgcn_fractf(v2);
 }
 
 // ---- Opt-in statistical RNG (F_XRNG, ptmi_scene_set_rng) ---------------------------
@@ -406,11 +366,6 @@ __device__ __forceinline__ void noise3d_pair(float x1, float y1, float z1, float
 struct Xrng {
     uint32_t s0, s1, s2, s3;
 };
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
 __device__ __forceinline__ float xnext(Xrng& r) {
     const uint32_t res = rotl32(r.s1 * 5u, 7) * 9u;
@@ -437,9 +392,6 @@ __device__ __forceinline__ float xnext16(Xrng& r) {
     r.s3 = rotl32(r.s3, 11);
     return (float)(res >> 16) * 0x1p-16f;
 }
-#ifndef PTMI_XSEED32
-#define PTMI_XSEED32 1
-#endif
 // 32-bit integer finaliser (lowbias32 form: two 32-bit multiplies, three xor-shifts).
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16;
@@ -449,7 +401,6 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16;
     return x;
 }
-#if PTMI_XSEED32
 // The pixel's stream key: its seed's 64 bits folded once per work item into two 32-bit
 // words (xseed_of), so a path seeds from (key, n) with 32-bit multiplies only.  xoshiro128**'s
 // state words s0 / s1 finalise (key.lo ^ nG) / (key.hi ^ nG), s2 / s3 finalise those mixed
@@ -476,22 +427,6 @@ __device__ __forceinline__ void xcamera(XSeed key, uint32_t n, float& rx, float&
     rx = (float)(mix32(((key.lo ^ g) + key.hi) ^ 0x68E31DA4u) >> 8) * 0x1p-24f;
     ry = (float)(mix32(((key.hi ^ g) + key.lo) ^ 0x1B56C4E9u) >> 8) * 0x1p-24f;
 }
-#else
-typedef uint64_t XSeed;
-__device__ __forceinline__ XSeed xseed_of(uint64_t seed_bits) { return seed_bits; }
-__device__ __forceinline__ Xrng xseed(XSeed seed_bits, uint32_t n) {
-    const uint64_t base = seed_bits ^ (0x9E3779B97F4A7C15ull * ((uint64_t)n + 1));
-    const uint64_t a = splitmix64(base + 0x9E3779B97F4A7C15ull), b = splitmix64(base + 0x3C6EF372FE94F82Aull);
-    Xrng r{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
-    if ((r.s0 | r.s1 | r.s2 | r.s3) == 0) r.s0 = 1;  // the all-zero state is the one fixed point
-    return r;
-}
-__device__ __forceinline__ void xcamera(XSeed seed_bits, uint32_t n, float& rx, float& ry) {
-    const uint64_t v = splitmix64(seed_bits + 0xD1B54A32D192ED03ull * ((uint64_t)n + 1));
-    rx = (float)(uint32_t)(v >> 40) * 0x1p-24f;
-    ry = (float)(uint32_t)((v >> 16) & 0xFFFFFFu) * 0x1p-24f;
-}
-#endif
 // checkAxis (tracer.cl:250-268)
 __device__ __forceinline__ void check_axis(double o, double d, double mn, double mx, double& t0, double& t1) {
     double a0 = mn - o, a1 = mx - o;
@@ -755,15 +690,6 @@ __device__ __forceinline__ void tri_uv(const DevTri& T, d4 o, d4 d, double& u, d
 #ifndef PTMI_STACK
 #define PTMI_STACK 24
 #endif
-#ifndef PTMI_GROUP_ACM
-#define PTMI_GROUP_ACM 1
-#endif
-#ifndef PTMI_GROUP_MASK
-#define PTMI_GROUP_MASK 1
-#endif
-#ifndef PTMI_NCUR_LDS
-#define PTMI_NCUR_LDS 1
-#endif
 // Per-lane LDS traversal stack: a Node4 visit pushes <= 3 entries and BVH4 chains are <= 7
 // nodes long (ptmi_bvh.cpp checks it), so a walk holds <= 21 entries.
 static constexpr int kStack = PTMI_STACK;
@@ -911,11 +837,7 @@ __device__ __forceinline__ bool key_entered(double k) { return __double2hiint(k)
 __device__ __forceinline__ int key_code(double k) { return __double2loint(k); }
 
 // The four child slab tests of Node4 `cur` (one walk step): keys of its children.
-#ifndef PTMI_STACKLESS
-#define PTMI_STACKLESS 0  // DIAGNOSTIC (study builds): the stackless walk (walk_index_stackless)
-#endif
-__device__ __forceinline__ void node_children(const DevScene& S, int cur, const WalkRay& W, float lim, double k[4],
-                                              int* parent = nullptr) {
+__device__ __forceinline__ void node_children(const DevScene& S, int cur, const WalkRay& W, float lim, double k[4]) {
     // The node's 64 B as four 16-B global loads issued together (one wait).  Bounds are
     // binary16 (ptmi_device.h), converted exactly to float inside v_fma_mix_f32, so the
     // slab test is the float-box one; a bound past the binary16 range is +-inf, whose
@@ -937,15 +859,7 @@ __device__ __forceinline__ void node_children(const DevScene& S, int cur, const 
     auto h16 = [](uint32_t w, int i) {
         return (float)__builtin_bit_cast(_Float16, (uint16_t)((i & 1) ? (w >> 16) : (w & 0xffffu)));
     };
-#if PTMI_STACKLESS
-    // (stackless study: child[0]'s high half holds the node's parent -- finalize_index_codes packs
-    // it for narrow-code scenes only, so wide codes keep all their bits)
-    const bool packed = S.leaf_bit == kLeafNarrow;
-    const int ch[4] = {(int)(packed ? (q[3].x & 0xFFFFu) : q[3].x), (int)q[3].y, (int)q[3].z, (int)q[3].w};
-    if (parent) *parent = (int)(q[3].x >> 16);
-#else
     const int ch[4] = {(int)q[3].x, (int)q[3].y, (int)q[3].z, (int)q[3].w};
-#endif
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         float tn = 0.0f, tf = lim;
@@ -1052,62 +966,6 @@ __device__ __forceinline__ void walk_index(const DevScene& S, Stk* __restrict__ 
     if (n_steps == 1) PTMI_COUNT(21);
 #endif
 }
-
-#if PTMI_STACKLESS
-// DIAGNOSTIC (study): the stackless form of walk_index that north_star names -- no traversal
-// stack: a walk keeps its node, the key of the child it last left (the next child is the
-// nearest entered one beyond it: child keys order children by (entry distance, code), the
-// order walk_index pushes them in) and, on the way up, the child it came from, whose key it
-// re-derives from the parent's re-tested children.  Each Node4 carries its parent in the
-// high half of child[0] (finalize_index_codes, PTMI_STACKLESS builds).  Every node is re-tested
-// once per child walked into; leaves are visited in the stack walk's order, so the candidates
-// and hence the winner are the same (the pruning limit only shrinks: a child culled on a
-// re-test lies beyond the best hit, and so do its later siblings).
-template <bool kVerify, typename RR>
-__device__ __forceinline__ void walk_index_stackless(const DevScene& S, const RR& R, int slot, int key, d4 o,
-                                                     d4 d, d4 rw, Hit& h, int& vchain) {
-    const WalkRay W = walk_setup(o, rw, R);
-    float lim = walk_limit(h.t);
-    int cur = R.entry;
-    if (cur >= kLeafNarrow) {  // a root that is a single leaf (or empty)
-        leaf_visit<kVerify>(S, cur - kLeafNarrow, slot, key, o, d, h, vchain);
-        return;
-    }
-    const int root = cur;
-    double thr = -__builtin_huge_val();  // children with keys above thr are still to walk
-    int from = -1;                        // the child node walked out of, or -1
-    while (true) {
-        double k[4];
-        int parent;
-        node_children(S, cur, W, lim, k, &parent);
-        if (from >= 0) {  // coming up from child `from`: resume after its key
-            thr = __builtin_huge_val();  // (from culled now: so is every later sibling)
-#pragma unroll
-            for (int i = 0; i < 4; i++) thr = key_code(k[i]) == from ? k[i] : thr;
-        }
-        double nk = __builtin_huge_val();
-#pragma unroll
-        for (int i = 0; i < 4; i++) nk = (key_entered(k[i]) && k[i] > thr) ? fmin(nk, k[i]) : nk;
-        if (nk == __builtin_huge_val()) {  // node exhausted
-            if (cur == root) break;
-            from = cur;
-            cur = parent;
-            continue;
-        }
-        const int c = key_code(nk);
-        if (c < kLeafNarrow) {
-            cur = c;
-            from = -1;
-            thr = -__builtin_huge_val();
-        } else {
-            leaf_visit<kVerify>(S, c - kLeafNarrow, slot, key, o, d, h, vchain);
-            lim = walk_limit(h.t);
-            from = -1;
-            thr = nk;
-        }
-    }
-}
-#endif
 
 // Candidate update as selects (no exec-mask branching).  t > EPSILON implies
 // the reference's `t != 0.0` recording test.
@@ -1304,46 +1162,12 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
             plane_take(P1, q1, k1);
         }
     }
-    // Affine planes after the floor / ceiling run: the +-0 entries of row1[0..2] skipped by their
-    // pattern (PlaneRec::nz, a uniform switch; round 6): walls rotated about one axis keep one exact
-    // zero (the reference scene's side walls (x, y), its back wall (y, z)).  Same terms in the same
-    // order, so the sums are bit-identical up to the sign of an exact zero (plane_rows_nz).
-    auto sum_nz = [&](auto nzc, const auto* m, double x, double y, double z) {
-        constexpr int NZ = decltype(nzc)::value;
-        double o = 0.0;
-        bool any = false;
-        if constexpr ((NZ & 1) != 0) {
-            o = m[0] * x;
-            any = true;
-        }
-        if constexpr ((NZ & 2) != 0) {
-            o = any ? o + m[1] * y : m[1] * y;
-            any = true;
-        }
-        if constexpr ((NZ & 4) != 0) o = any ? o + m[2] * z : m[2] * z;
-        return o;
-    };
-    auto par_pair = [&](auto nzc, const auto& P0, const auto& P1, double& q0, bool& k0, double& q1, bool& k1,
-                        int pi) {
-        const auto* m = P0.row1;
-        [[maybe_unused]] const double a = sum_nz(nzc, m, ro.x, ro.y, ro.z);
-        const double dy = sum_nz(nzc, m, rd.x, rd.y, rd.z);
-        plane_q2(pterm(pi, [&] { return a + m[3]; }), pterm(pi + 1, [&] { return a + P1.row1[3]; }), dy, q0, k0, q1,
-                 k1);
-    };
     for (; p + 1 < np; p += 2) {
         PTMI_WADD(48, 1ull);
         const auto &P0 = cmem(S.planes)[p], &P1 = cmem(S.planes)[p + 1];
         double oy0, dy0, oy1, dy1, q0, q1;
         bool k0, k1;
-        if (A && P0.par && PTMI_R6_PLNZ) {
-            switch (P0.nz) {
-                case 3: par_pair(std::integral_constant<int, 3>(), P0, P1, q0, k0, q1, k1, p); break;
-                case 5: par_pair(std::integral_constant<int, 5>(), P0, P1, q0, k0, q1, k1, p); break;
-                case 6: par_pair(std::integral_constant<int, 6>(), P0, P1, q0, k0, q1, k1, p); break;
-                default: par_pair(std::integral_constant<int, 7>(), P0, P1, q0, k0, q1, k1, p); break;
-            }
-        } else if (A && P0.par) {  // parallel pair: one sum of the origin's x, y, z terms, one direction term
+        if (A && P0.par) {  // parallel pair: one sum of the origin's x, y, z terms, one direction term
             const auto* m = P0.row1;  // and one reciprocal (row1[0..2] of P1 are the same bits)
             [[maybe_unused]] const double a = (m[0] * ro.x + m[1] * ro.y) + m[2] * ro.z;
             oy0 = pterm(p, [&] { return a + m[3]; });
@@ -1364,18 +1188,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         const auto& P0 = cmem(S.planes)[p];
         double q0;
         bool k0;
-        if (A && PTMI_R6_PLNZ) {
-            double oy, dy;
-            switch (P0.nz) {
-                case 3: plane_rows_nz<3, CAM>(P0.row1, ro, rd, oy, dy, cpl, p); break;
-                case 5: plane_rows_nz<5, CAM>(P0.row1, ro, rd, oy, dy, cpl, p); break;
-                case 6: plane_rows_nz<6, CAM>(P0.row1, ro, rd, oy, dy, cpl, p); break;
-                default: plane_rows(P0, oy, dy, p); break;
-            }
-            plane_q(oy, dy, q0, k0);
-        } else {
-            plane_t(P0, q0, k0, p);
-        }
+        plane_t(P0, q0, k0, p);
         plane_take(P0, q0, k0);
     }
     const int nq = (PTMI_ABLATE & 16) ? 0 : S.n_spheres_st;
@@ -1432,7 +1245,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         pend = disc > 0.0;
     };
     int q = 0;
-    if (PTMI_R6_SPH && nq == 1) {
+    if (nq == 1) {
         const auto& Q0 = cmem(S.spheres)[0];
         d4 o0, d0;
         sphere_ray(Q0, o0, d0, csp + kCamSphere * q);
@@ -1441,7 +1254,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         first(a0, b0, disc0, Q0.slot, Q0.key);
         q = 1;
     }
-    if (PTMI_R6_SPH && nq >= 2) {
+    if (nq >= 2) {
         PTMI_WADD(50, 1ull);
         const auto &Q0 = cmem(S.spheres)[0], &Q1 = cmem(S.spheres)[1];
         d4 o0, d0, o1, d1;
@@ -1473,7 +1286,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         sphere_ray(Q0, o0, d0, csp + kCamSphere * q);
         double a0, b0, disc0;
         sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * q);
-        defer(a0, b0, disc0, Q0.slot, Q0.key);  // (q >= 2 here when PTMI_R6_SPH: the first sphere is peeled)
+        defer(a0, b0, disc0, Q0.slot, Q0.key);  // (q >= 2 here: the first sphere is peeled)
     }
     if (pend) {
         PTMI_WADD(33, 1ull);
@@ -1482,7 +1295,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
     int j = S.run_end[0];
     // spheres with other matrices (none when every sphere is in S.spheres: the loop's scalar
     // record loads and waits are skipped)
-    if (PTMI_R6_SPH && S.run_end[1] - j == S.n_spheres_st) j = S.run_end[1];
+    if (S.run_end[1] - j == S.n_spheres_st) j = S.run_end[1];
     for (; j < S.run_end[1]; j++) {
         PTMI_WADD(53, 1ull);
         const auto& ob = cmem(S.objs)[j];
@@ -1577,10 +1390,6 @@ __device__ __forceinline__ void group_walks_impl(const DevScene& S, Stk* __restr
                          R.hull_mx[2], h.t + prune_margin(h.t), tn))
                 continue;
             PTMI_TSTAMP(t_w);
-#if PTMI_STACKLESS
-            if constexpr (A && sizeof(Stk) == 2) walk_index_stackless<kVerify>(S, R, j, ob.key, o, d, r, h, vchain);
-            else
-#endif
             walk_index<kVerify>(S, stk, R, j, ob.key, o, d, r, h, vchain);
             PTMI_TADD_ACTIVE(18, t_w);  // (stats: cycles in walk loops)
         }
@@ -1681,12 +1490,8 @@ __device__ __forceinline__ void hemi_sqrt(float u2, double& r2s, double& rc) {
 // also counts records where the generic sequences differ -- they never read the table --
 // and ptmi_diag_hemi_mismatch reports the count, 0 on this toolchain).  Off-grid draws
 // compute; the statistical mode draws its hemisphere uniforms on the grid (xnext16).
-#ifndef PTMI_HEMI_TAB_GROUPS
-#define PTMI_HEMI_TAB_GROUPS 1  // mesh scenes read the table too (round 5: with the group kernel's colour
-                                // state in LDS, 2048 spp: C4 594 -> 577, C5 902 -> 897 ms; in round 4 the
-                                // 2 MB table's L2 share had cost C5 ~1.5 % at 512 spp); since round 6 a scene
-                                // switch as well (DevScene::hemi_mesh, ptmi_api.cpp; on by default)
-#endif
+// Mesh scenes read the table too, unless the scene says otherwise (DevScene::hemi_mesh, ptmi_api.cpp;
+// on by default).
 static constexpr int kHemiBits = 16;
 static constexpr int kHemiSize = 1 << kHemiBits;
 __device__ __forceinline__ int hemi_slot(float u) {  // table record of u, or -1 off the grid
@@ -1694,8 +1499,7 @@ __device__ __forceinline__ int hemi_slot(float u) {  // table record of u, or -1
     const int k = (int)t;
     // Every uniform is in [0, 1) (noise3d's fract is at most 0x1.fffffep-1, xnext16 < 1), so k is
     // below kHemiSize whenever t is an integer; a NaN fails the equality.
-    if (PTMI_R6_SLOT) return t == (float)k ? k : -1;
-    return (t == (float)k && (unsigned)k < (unsigned)kHemiSize) ? k : -1;
+    return t == (float)k ? k : -1;
 }
 
 // The table is two planes (round 6): [0, 2^16) the (sin, cos) pairs, [2^16, 2^17) the (sqrt u,
@@ -1703,9 +1507,6 @@ __device__ __forceinline__ int hemi_slot(float u) {  // table record of u, or -1
 // unrelated records (u1 and u2 are independent draws); the planes let the mesh kernels keep just the
 // 1-MB (sin, cos) plane in the L2 they share with the traversal index and compute the sqrt pair
 // (kTabSqrt false): with the whole 2-MB table their HBM traffic was the table's evictions.
-#ifndef PTMI_HEMI_SQRT_GROUPS
-#define PTMI_HEMI_SQRT_GROUPS 0  // mesh kernels read the sqrt plane too (1) or compute the pair (0)
-#endif
 // `use` (uniform): the scene lets this kernel read the table (DevScene::hemi_mesh for the mesh kernels).
 template <bool A, bool kTab, bool kTabSqrt = kTab>
 __device__ __forceinline__ d4 random_hemisphere(const double* __restrict__ tab, d4 nv, float u1, float u2,
@@ -1782,12 +1583,7 @@ __device__ __noinline__ void sunflower(int amount, int point, double& ox, double
 // 160.89 -> 154.46 / 157.35 ms, C4 (512 spp) 165.84 -> 165.15 ms (profiles/r4/cam_reload).
 // A *volatile* asm here made every later global load of the loop a vector load (the
 // uniform-load analysis treats it as a possible store): C2 264 ms.
-#ifndef PTMI_CAM_RELOAD
-#define PTMI_CAM_RELOAD 3  // 1: kernels without meshes, 2: mesh kernels, 3: both
-#endif
-template <bool kReload = true>
 __device__ __forceinline__ const DevCamera& camera_ptr(const DevScene& S) {
-    if constexpr (!kReload) return S.cam;
     // The constant address space: scalar loads of an invariant record (through a generic
     // pointer the loads were per-lane vector loads: C2 155 -> 264 ms).
     // readfirstlane: a value divergence analysis knows to be uniform, so the loads are
@@ -1999,11 +1795,11 @@ __device__ __noinline__ d4 plane_normal_map(const DevTexArray T, const DevObject
 // kMaskLds: the path's mask (throughput) lives in LDS at msk[0, kBlock, 2 kBlock] instead of
 // P.mr/mg/mb (the mesh kernels, where the 4-wave register budget otherwise spills it with a
 // scratch load and store per bounce).
-// Which instantiations take the lockstep item loop (PTMI_LOCKSTEP): all-diffuse affine scenes without
+// Which instantiations take the lockstep item loop: all-diffuse affine scenes without
 // meshes or textures.  There every hit is an effective bounce (no reflection or refraction), so the
 // bounce index b is also effectiveBounces, and a path has at most kMaxEffectiveBounces records.
 template <int FL>
-constexpr bool kLockstepOf = PTMI_LOCKSTEP != 0 && !(FL & (F_GROUPS | F_MATERIALS | F_PROJ | F_TEX));
+constexpr bool kLockstepOf = !(FL & (F_GROUPS | F_MATERIALS | F_PROJ | F_TEX));
 
 // A path's last bounce record (lockstep loop): the path ends at this hit -- the object is emissive
 // (tracer.cl:1107) or effectiveBounces reaches its bound (tracer.cl:884) -- and the reduction
@@ -2146,9 +1942,8 @@ __device__ __forceinline__ bool bounce_shade(const DevScene& S, PathState& P, co
         }
         // Only affine instantiations read the table: its records are the affine sequences'
         // results, so they equal what such a lane computes by construction.
-        P.rd = random_hemisphere<A, A && (PTMI_HEMI_TAB_GROUPS || !(FL & F_GROUPS)),
-                                 A && (PTMI_HEMI_SQRT_GROUPS || !(FL & F_GROUPS))>(S.hemi, nv, u1, u2,
-                                                                                 !(FL & F_GROUPS) || S.hemi_mesh);
+        // The mesh kernels read the (sin, cos) plane only and compute the sqrt pair (random_hemisphere).
+        P.rd = random_hemisphere<A, A, A && !(FL & F_GROUPS)>(S.hemi, nv, u1, u2, !(FL & F_GROUPS) || S.hemi_mesh);
         cosine = dotv<A>(P.rd, nv);
     }
     P.ro = over;
@@ -2234,7 +2029,7 @@ __device__ __forceinline__ bool bounce_shade(const DevScene& S, PathState& P, co
 // Per-launch resources of trace_kernel<FL>: workgroup size and the register budget.
 #ifndef PTMI_WAVES
 #define PTMI_WAVES 7  // waves/SIMD the register allocation targets (scenes without groups or materials).
-                      // Round 6: with the colour sums really in LDS (PTMI_R6_VACC) and the bounce-loop
+                      // Round 6: with the colour sums really in LDS (trace_kernel) and the bounce-loop
                       // cuts, C2's kernel fits 72 VGPRs without spill and C3's 72 with 16 B/lane: 7 waves,
                       // C2 150.5 -> 145.1 ms, C3 153.0 -> 152.0 ms (profiles/r6/SUMMARY.md).  Before:
                       // With the sincos constants in SGPRs (ptmi_fp64core.h) C2/C3 fit 95 VGPRs at 5 waves
@@ -2243,7 +2038,7 @@ __device__ __forceinline__ bool bounce_shade(const DevScene& S, PathState& P, co
                       // 167.9, C3 179.5 -> 174.9 ms); 7 waves (72 VGPRs, 96 B/lane) lose 10 %
 #endif
 #ifndef PTMI_WAVES_LOCKSTEP_DOF
-#define PTMI_WAVES_LOCKSTEP_DOF 7  // ... the lockstep loop with DoF.  Staged (PTMI_STAGES) it needs 75 VGPRs without
+#define PTMI_WAVES_LOCKSTEP_DOF 7  // ... the lockstep loop with DoF.  Staged it needs 75 VGPRs without
                                    // scratch, and 7 waves win: same box, 2048 spp, C3 114.0-114.5 ms at 7 waves,
                                    // 118.1-118.3 at 6 (C2, no DoF: 110.4-110.7 at 7, 114.9-115.3 at 6;
                                    // profiles/stages/SUMMARY.md).  The single loop spilled 48 B/lane at 72 VGPRs
@@ -2333,8 +2128,7 @@ __device__ __forceinline__ Item work_item(const DevScene& S, const WorkPlan& WP,
 // adds 0.
 __device__ __forceinline__ double mom_q(double r, double g, double b) { return (r * r + g * g) + b * b; }
 // Where an item's second moment goes: a whole-tile item's into sq[pixel]; a chunk item's into one
-// more plane of the partial buffer, after the 3 colour planes (kPlanes) or the 4-double records.
-template <bool kPlanes>
+// more plane of the partial buffer, after the 3 colour planes.
 __device__ __forceinline__ void store_mom(const Item& it, const WorkPlan& WP, double* __restrict__ sq,
                                           double* __restrict__ part, double m2) {
     if (!it.inside) return;
@@ -2343,54 +2137,30 @@ __device__ __forceinline__ void store_mom(const Item& it, const WorkPlan& WP, do
         return;
     }
     const size_t plane = (size_t)WP.nchunks * WP.n_tail * 64;
-    __builtin_nontemporal_store(m2, part + (kPlanes ? 3 : 4) * plane + it.oslot);
+    __builtin_nontemporal_store(m2, part + 3 * plane + it.oslot);
 }
 
-// A whole-tile item writes its pixel's (r, g, b, samples) into the frame sums.  A chunk
-// item: kPlanes, its r, g, b into plane k of the partial buffer at
-// k * (nchunks * n_tail * 64) + oslot, the sample counts re-derived by reduce_chunks_kernel
-// (24 B per lane and item); else the same (r, g, b, samples) record as a whole tile.  The
-// stores are non-temporal: written once, read by the reduce after the launch, they should not
-// evict the mesh index and the hemisphere table from an XCD's L2.
-// Round 3 kept the mesh kernels on records (the plane store then cost them 9 more spill
-// reloads in the loop, C4/C5 +2 %; the row layout [(item * 3 + k) * 64 + lane] cost C2
-// +0.3 %).  Round 6, where the mesh kernel stores after its loop from a re-derived item:
-// planes C4 533.4 / 532.6 -> 529.7 / 531.1 ms, C5 828.5 / 826.8 -> 823.0 / 824.8; planes and
-// non-temporal stores 528.9 / 530.8 and 822.2 / 825.5 ms, C2 unchanged (145.2 / 145.0 ->
-// 145.2 / 145.1); HBM per launch C4 1.05 -> 0.88 GB, C5 3.71 -> 3.36 GB (profiles/r6/traffic).
-#ifndef PTMI_NT_SUMS
-#define PTMI_NT_SUMS 1
-#endif
-template <bool kPlanes>
+// A whole-tile item writes its pixel's (r, g, b, samples) into the frame sums.  A chunk item writes
+// its r, g, b into plane k of the partial buffer at k * (nchunks * n_tail * 64) + oslot, the sample
+// counts re-derived by reduce_chunks_kernel (24 B per lane and item).  The stores are non-temporal:
+// written once, read by the reduce after the launch, they should not evict the mesh index and the
+// hemisphere table from an XCD's L2.
 __device__ __forceinline__ void store_sums(const Item& it, const WorkPlan& WP, double* __restrict__ sums,
                                            double* __restrict__ part, double cr, double cg, double cb) {
     if (!it.inside) return;
-    if (kPlanes && !it.whole) {
+    if (!it.whole) {
         const size_t plane = (size_t)WP.nchunks * WP.n_tail * 64;
-        if (PTMI_NT_SUMS) {
-            __builtin_nontemporal_store(cr, part + it.oslot);
-            __builtin_nontemporal_store(cg, part + plane + it.oslot);
-            __builtin_nontemporal_store(cb, part + 2 * plane + it.oslot);
-            return;
-        }
-        part[it.oslot] = cr;
-        part[plane + it.oslot] = cg;
-        part[2 * plane + it.oslot] = cb;
+        __builtin_nontemporal_store(cr, part + it.oslot);
+        __builtin_nontemporal_store(cg, part + plane + it.oslot);
+        __builtin_nontemporal_store(cb, part + 2 * plane + it.oslot);
         return;
     }
-    double* o = (it.whole ? sums : part) + it.oslot * 4;
+    double* o = sums + it.oslot * 4;
     const double ns = (double)(it.c1 > it.c0 ? it.c1 - it.c0 : 0);
-    if (PTMI_NT_SUMS) {
-        __builtin_nontemporal_store(cr, o + 0);
-        __builtin_nontemporal_store(cg, o + 1);
-        __builtin_nontemporal_store(cb, o + 2);
-        __builtin_nontemporal_store(ns, o + 3);
-        return;
-    }
-    o[0] = cr;
-    o[1] = cg;
-    o[2] = cb;
-    o[3] = ns;
+    __builtin_nontemporal_store(cr, o + 0);
+    __builtin_nontemporal_store(cg, o + 1);
+    __builtin_nontemporal_store(cb, o + 2);
+    __builtin_nontemporal_store(ns, o + 3);
 }
 
 // The scene record through an opaque uniform pointer to the kernel's arguments (DevScene is
@@ -2398,13 +2168,8 @@ __device__ __forceinline__ void store_sums(const Item& it, const WorkPlan& WP, d
 // they are used instead of being held in SGPRs across the loop (camera_ptr's reasoning):
 // fewer SGPRs live across the loop, fewer of them spilled to VGPR lanes (the C2 loop's
 // static v_readlane count 32 -> 18).  2048 spp, one MI355X (profiles/r5/SUMMARY.md s6):
-// C3 158.4 -> 156.3 ms; with PTMI_HEMI_TAB_GROUPS C4 577 -> 561, C5 897 -> 882 ms; C2 unchanged.
-#ifndef PTMI_SCENE_RELOAD
-#define PTMI_SCENE_RELOAD 3  // 1: mesh kernels, 2: kernels without meshes, 3: both (0: off)
-#endif
-template <bool kReload>
+// C3 158.4 -> 156.3 ms; C4 577 -> 561, C5 897 -> 882 ms; C2 unchanged.
 __device__ __forceinline__ const DevScene& scene_reload(const DevScene& S) {
-    if constexpr (!kReload) return S;
     typedef const __attribute__((address_space(4))) DevScene ConstScene;
     const DevScene* p = (const DevScene*)__builtin_amdgcn_kernarg_segment_ptr();
     asm("" : "+s"(p));
@@ -2468,11 +2233,9 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
     // accumColor of the lane's current path in LDS (bounce_shade kAccLds), as in the kernels
     // without meshes: it changes only on bounces that see emission, and in registers the
     // 4-wave budget spilled it with a load and a store per bounce.
-    constexpr bool kAcm = PTMI_GROUP_ACM != 0;
-    __shared__ double acm_lds[kAcm ? 3 * kBlock : 1];
+    __shared__ double acm_lds[3 * kBlock];
     // ... and the path's mask (bounce_shade kMaskLds).
-    constexpr bool kMsk = PTMI_GROUP_MASK != 0;
-    __shared__ double msk_lds[kMsk ? 3 * kBlock : 1];
+    __shared__ double msk_lds[3 * kBlock];
     __shared__ double hp_t_lds[kBlock];
     __shared__ int hp_pk_lds[kBlock];
     __shared__ double cam_lds[kCamComp * kBlock];
@@ -2490,12 +2253,9 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
     const XSeed seed_bits = xseed_of((uint64_t)__double_as_longlong(seed));  // statistical mode
     const uint32_t c_end = it.inside ? it.c1 : it.c0;
     auto* stk = lds_ptr(stk_lds + tid);
-#if PTMI_R6_VACC  // (the colour sums really in LDS: see trace_kernel)
+    // (the colour sums really in LDS: see trace_kernel)
     volatile __attribute__((address_space(3))) double* acc =
         (volatile __attribute__((address_space(3))) double*)(acc_lds + tid);
-#else
-    double* acc = acc_lds + tid;
-#endif
     acc[0 * kBlock] = 0.0;
     acc[1 * kBlock] = 0.0;
     acc[2 * kBlock] = 0.0;
@@ -2504,30 +2264,26 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
     volatile __attribute__((address_space(3))) double* m2 =
         (volatile __attribute__((address_space(3))) double*)(m2_lds + (kMom ? tid : 0));
     if constexpr (kMom) m2[0] = 0.0;
-    double* acm = kAcm ? acm_lds + tid : nullptr;
-    double* msk = kMsk ? msk_lds + tid : nullptr;
+    double* acm = acm_lds + tid;
+    double* msk = msk_lds + tid;
     uint32_t n_gen = it.c0;
-#if PTMI_NCUR_LDS
     // The sample index of the lane's current path waits in LDS (written at path start, read by
     // the shading's noise draws): in registers the 4-wave budget spilled it, a scratch store at
     // nearly every loop iteration.
     __shared__ uint32_t ncur_lds[kBlock];
-#else
-    uint32_t n_cur = 0;
-#endif
     bool buffered = false, active = false, pending = false;
     PathState P;
     PTMI_TSTAMP(t_loop);
     for (;;) {
         if (!__any(active || buffered || n_gen < c_end)) break;
-        const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 1) != 0>(S0);
+        const DevScene& S = scene_reload(S0);
         PTMI_TSTAMP(t_a);
         // Camera rays in wave-wide batches (see trace_kernel).
         const bool need = !buffered && n_gen < c_end;
         const int n_need = __popcll(__ballot(need));
         const int n_starve = __popcll(__ballot(!buffered && !active && n_gen < c_end));
         if (n_need >= kRefillNeed || n_starve >= PTMI_REFILL_STARVE_GROUPS || (n_starve > 0 && !__any(active))) {
-            const DevCamera& cam = camera_ptr<(PTMI_CAM_RELOAD & 2) != 0>(S);
+            const DevCamera& cam = camera_ptr(S);
             if (need) {
                 d4 ro, rd;
                 float rx, ry;
@@ -2558,25 +2314,17 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
                 cro = mk(cb[3 * kBlock], cb[4 * kBlock], cb[5 * kBlock], A ? 1.0 : cb[(kCamComp - 2) * kBlock]);
             else
                 {
-                    const double* co = camera_ptr<(PTMI_CAM_RELOAD & 2) != 0>(S).origin;  // ray_for_pixel's origin
+                    const double* co = camera_ptr(S).origin;  // ray_for_pixel's origin
                     cro = mk(co[0], co[1], co[2], 1.0);
                 }
             start_path<A, kDof>(P, cro, crd);
-            if constexpr (kAcm) {
-                acm[0 * kBlock] = 0.0;
-                acm[1 * kBlock] = 0.0;
-                acm[2 * kBlock] = 0.0;
-            }
-            if constexpr (kMsk) {
-                msk[0 * kBlock] = 1.0;
-                msk[1 * kBlock] = 1.0;
-                msk[2 * kBlock] = 1.0;
-            }
-#if PTMI_NCUR_LDS
+            acm[0 * kBlock] = 0.0;
+            acm[1 * kBlock] = 0.0;
+            acm[2 * kBlock] = 0.0;
+            msk[0 * kBlock] = 1.0;
+            msk[1 * kBlock] = 1.0;
+            msk[2 * kBlock] = 1.0;
             ncur_lds[tid] = n_gen - 1;
-#else
-            n_cur = n_gen - 1;
-#endif
             if constexpr ((FL & F_XRNG) != 0) P.rng = xseed(seed_bits, n_gen - 1);
             buffered = false;
             active = true;
@@ -2626,22 +2374,11 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
         }
         PTMI_TADD(14, t_c);
         PTMI_TSTAMP(t_d);
-#if PTMI_NCUR_LDS
-        if (ready && bounce_shade<FL, kAcm, kMsk>(S, P, h, fgi, ncur_lds[tid], acm, msk)) {
-#else
-        if (ready && bounce_shade<FL, kAcm, kMsk>(S, P, h, fgi, n_cur, acm, msk)) {
-#endif
-            if constexpr (kAcm) {
-                acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
-                acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
-                acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
-                if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
-            } else {
-                acc[0 * kBlock] = acc[0 * kBlock] + P.ar;
-                acc[1 * kBlock] = acc[1 * kBlock] + P.ag;
-                acc[2 * kBlock] = acc[2 * kBlock] + P.ab;
-                if constexpr (kMom) m2[0] = m2[0] + mom_q(P.ar, P.ag, P.ab);
-            }
+        if (ready && bounce_shade<FL, true, true>(S, P, h, fgi, ncur_lds[tid], acm, msk)) {
+            acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
+            acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
+            acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
+            if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
             active = false;
         }
         PTMI_TADD(15, t_d);
@@ -2662,9 +2399,9 @@ __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t sample
 #endif
     // The work item is re-derived (a few integer operations) rather than kept live across
     // the loop: its fields would hold ~5 VGPRs through every walk phase.
-    store_sums<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S, WP, item, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock], acc[2 * kBlock]);
+    store_sums(work_item<kTilesOf<FL>>(S, WP, item, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock], acc[2 * kBlock]);
     if constexpr (kMom)
-        store_mom<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S, WP, item, lane), WP, sq, part, m2[0]);
+        store_mom(work_item<kTilesOf<FL>>(S, WP, item, lane), WP, sq, part, m2[0]);
 }
 
 // trace_groups with the path pool (kPoolOf above): the same loop, phases and walks; what
@@ -2724,7 +2461,7 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
     PathState P;
     for (;;) {
         if (!__any(active || buffered) && j_next >= total) break;
-        const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 1) != 0>(S0);
+        const DevScene& S = scene_reload(S0);
         // Camera rays in wave-wide batches, as trace_groups; the lanes without a buffered ray take
         // the next paths, idle lanes first.
         const uint32_t avail = total - j_next;
@@ -2745,7 +2482,7 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
                 const bool in = px < W && py < H;
                 const double sd = in ? seeds[(uint32_t)py * (uint32_t)W + (uint32_t)px] : 0.0;
                 const float fgi2 = (float)(sd / (double)samples);
-                const DevCamera& cam = camera_ptr<(PTMI_CAM_RELOAD & 2) != 0>(S);
+                const DevCamera& cam = camera_ptr(S);
                 d4 ro, rd;
                 float rx, ry;
                 camera_offsets<FL>(fgi_lds[p], fgi2, XSeed{}, n, rx, ry);
@@ -2771,7 +2508,7 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
             if constexpr (kCamComp > 3) {
                 cro = mk(cb[3 * kBlock], cb[4 * kBlock], cb[5 * kBlock], 1.0);
             } else {
-                const double* co = camera_ptr<(PTMI_CAM_RELOAD & 2) != 0>(S).origin;
+                const double* co = camera_ptr(S).origin;
                 cro = mk(co[0], co[1], co[2], 1.0);
             }
             start_path<A, kDof>(P, cro, crd);
@@ -2827,144 +2564,10 @@ __device__ __forceinline__ void trace_groups_pool(const DevScene& S0, uint32_t s
         }
     }
     __builtin_amdgcn_wave_barrier();
-    store_sums<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S0, WP, item, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
+    store_sums(work_item<kTilesOf<FL>>(S0, WP, item, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
                                       acc_lds[1 * kBlock + tid], acc_lds[2 * kBlock + tid]);
     if constexpr (kMom)
-        store_mom<PTMI_MESH_PLANES != 0>(work_item<kTilesOf<FL>>(S0, WP, item, lane), WP, sq, part, m2_lds[tid]);
-}
-
-// The path pool for the kernels without meshes (PTMI_POOL_FLAT, affine non-DoF parity-mode scenes):
-// the loop of trace_kernel's else branch with trace_groups_pool's path hand-out.  Measured and off:
-// their items are mostly whole tiles (2048 samples per lane, no per-item drain to remove), and what
-// the pool saves in registers (C2: 69 instead of 72 VGPRs at 7 waves, or 8 waves at 64 VGPRs with
-// 16 B/lane of spill, 5,120 B of LDS) does not pay for its LDS reads and atomics: 2048 spp, same
-// box, C2 144.46 ms -> 146.9 (7 waves) / 145.3 ms (8 waves) (profiles/r6/tune/ab2).
-#ifndef PTMI_POOL_FLAT
-#define PTMI_POOL_FLAT 0
-#endif
-#ifndef PTMI_POOL_FGI2_SEED
-#define PTMI_POOL_FGI2_SEED 1  // fgi2 recomputed from the seed at the camera refill (no LDS table)
-#endif
-template <int FL>
-constexpr bool kPoolFlatOf = PTMI_POOL_FLAT != 0 && !(FL & (F_GROUPS | F_PROJ | F_XRNG | F_TEX | F_DOF));
-template <int FL>
-__device__ __forceinline__ void trace_flat_pool(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
-                                                const double* __restrict__ seeds, const double* __restrict__ sunf,
-                                                double* __restrict__ sums, double* __restrict__ part,
-                                                double* __restrict__ sq) {
-    constexpr bool A = true;
-    constexpr bool kDof = (FL & F_DOF) != 0;
-    constexpr bool kMom = (FL & F_MOM) != 0;
-    constexpr int kCamComp = kDof ? 6 : 3;
-    __shared__ double m2_lds[kMom ? kBlock : 1];
-    __shared__ double acc_lds[3 * kBlock];
-    __shared__ double acm_lds[3 * kBlock];
-    __shared__ double cam_lds[kCamComp * kBlock];
-    __shared__ uint32_t ncur_lds[kBlock];
-    __shared__ float fgi_lds[kBlock];
-    __shared__ float fgi2_lds[PTMI_POOL_FGI2_SEED ? 1 : kBlock];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const Item it = work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane);
-    if (!it.ok) return;
-    {
-        const double seed0 = it.inside ? seeds[it.i] : 0.0;
-        fgi_lds[tid] = (float)(seed0 / (double)S0.n_list);
-        if (!PTMI_POOL_FGI2_SEED) fgi2_lds[tid] = (float)(seed0 / (double)samples);
-    }
-    const int W = S0.cam.width, H = S0.cam.height;
-    acc_lds[0 * kBlock + tid] = 0.0;
-    acc_lds[1 * kBlock + tid] = 0.0;
-    acc_lds[2 * kBlock + tid] = 0.0;
-    if constexpr (kMom) m2_lds[tid] = 0.0;
-    __builtin_amdgcn_wave_barrier();  // (see trace_groups_pool)
-    const int tx0 = __builtin_amdgcn_readfirstlane(it.px - (lane & 7));
-    const int ty0 = __builtin_amdgcn_readfirstlane(it.py - (lane >> 3));
-    const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)it.c0);
-    const uint32_t total = 64u * ((uint32_t)__builtin_amdgcn_readfirstlane((int)it.c1) - c0);
-    double* acm = acm_lds + tid;
-    uint32_t j_next = 0, buf_id = 0;
-    bool buffered = false, active = false;
-    PathState P;
-    for (;;) {
-        if (!__any(active || buffered) && j_next >= total) break;
-        const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
-        const uint32_t avail = total - j_next;
-        const uint64_t m_idle = __ballot(!buffered && !active), m_busy = __ballot(!buffered && active);
-        const uint32_t n_idle = min((uint32_t)__popcll(m_idle), avail);
-        const uint32_t n_need = min((uint32_t)(__popcll(m_idle) + __popcll(m_busy)), avail);
-        if (n_need >= (uint32_t)kRefillNeed || n_idle >= (uint32_t)PTMI_REFILL_STARVE || (n_idle > 0 && !__any(active))) {
-            const uint32_t rank = active ? (uint32_t)__popcll(m_idle) + __builtin_amdgcn_mbcnt_hi(
-                                                                            (uint32_t)(m_busy >> 32),
-                                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)m_busy, 0u))
-                                         : __builtin_amdgcn_mbcnt_hi((uint32_t)(m_idle >> 32),
-                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)m_idle, 0u));
-            if (!buffered && rank < avail) {
-                const uint32_t j = j_next + rank;
-                const uint32_t p = j & 63u, n = c0 + (j >> 6);
-                const int px = tx0 + (int)(p & 7u), py = ty0 + (int)(p >> 3);
-                float fgi2;
-                if (PTMI_POOL_FGI2_SEED) {
-                    const double sd = (px < W && py < H) ? seeds[(uint32_t)py * (uint32_t)W + (uint32_t)px] : 0.0;
-                    fgi2 = (float)(sd / (double)samples);
-                } else {
-                    fgi2 = fgi2_lds[p];
-                }
-                const DevCamera& cam = camera_ptr<(PTMI_CAM_RELOAD & 1) != 0>(S);
-                d4 ro, rd;
-                float rx, ry;
-                camera_offsets<FL>(fgi_lds[p], fgi2, XSeed{}, n, rx, ry);
-                ray_for_pixel<kDof, A>(cam, sunf, (unsigned)px, (unsigned)py, rx, ry, (int)n, ro, rd);
-                double* cb = cam_lds + tid;
-                cb[0 * kBlock] = rd.x;
-                cb[1 * kBlock] = rd.y;
-                cb[2 * kBlock] = rd.z;
-                if constexpr (kCamComp > 3) {
-                    cb[3 * kBlock] = ro.x;
-                    cb[4 * kBlock] = ro.y;
-                    cb[5 * kBlock] = ro.z;
-                }
-                buf_id = j;
-                buffered = true;
-            }
-            j_next += n_need;
-        }
-        if (!active && buffered) {
-            const double* cb = cam_lds + tid;
-            const d4 crd = mk(cb[0 * kBlock], cb[1 * kBlock], cb[2 * kBlock], 0.0);
-            d4 cro;
-            if constexpr (kCamComp > 3) {
-                cro = mk(cb[3 * kBlock], cb[4 * kBlock], cb[5 * kBlock], 1.0);
-            } else {
-                const double* co = camera_ptr<(PTMI_CAM_RELOAD & 1) != 0>(S).origin;
-                cro = mk(co[0], co[1], co[2], 1.0);
-            }
-            start_path<A, kDof>(P, cro, crd);
-            acm[0 * kBlock] = 0.0;
-            acm[1 * kBlock] = 0.0;
-            acm[2 * kBlock] = 0.0;
-            ncur_lds[tid] = buf_id;
-            buffered = false;
-            active = true;
-        }
-        if (active) {
-            Hit h;
-            if (P.dead) h.pk = -1;
-            else h = find_closest_prims<FL>(S, P.ro, P.rd);
-            const uint32_t id = ncur_lds[tid];
-            if (bounce_shade<FL, true>(S, P, h, fgi_lds[id & 63u], c0 + (id >> 6), acm)) {
-                const uint32_t p = id & 63u;
-                atomicAdd(&acc_lds[0 * kBlock + p], acm[0 * kBlock]);
-                atomicAdd(&acc_lds[1 * kBlock + p], acm[1 * kBlock]);
-                atomicAdd(&acc_lds[2 * kBlock + p], acm[2 * kBlock]);
-                if constexpr (kMom) atomicAdd(&m2_lds[p], mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]));
-                active = false;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    store_sums<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sums, part, acc_lds[0 * kBlock + tid],
-                     acc_lds[1 * kBlock + tid], acc_lds[2 * kBlock + tid]);
-    if constexpr (kMom) store_mom<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sq, part, m2_lds[tid]);
+        store_mom(work_item<kTilesOf<FL>>(S0, WP, item, lane), WP, sq, part, m2_lds[tid]);
 }
 
 // Per-item duration onto its tile's cost accumulator (WorkPlan::cost, tile_order_kernel;
@@ -2992,7 +2595,7 @@ __device__ __forceinline__ void item_cost_add(const DevScene& S, const WorkPlan&
 // over the whole sample range (sums -> the frame) or a sample chunk of a tail tile
 // (sums -> its slot of the partial buffer).  A wave that finishes frees its slot (LDS
 // included) at once.  RGB sums, A = #samples.
-// Which item a mesh kernel's workgroup runs: PTMI_ITEM_QUEUE 1 -- the next one in dispatch
+// Which item a mesh kernel's workgroup runs: the next one in dispatch
 // order from a per-launch counter (one atomic per workgroup, zeroed before the launch), so
 // items go to whichever XCD frees a slot first instead of workgroup b's fixed XCD (b mod 8),
 // whose static eighth of the items made the XCDs of an 8-rank C5 share end up to 8 ms apart
@@ -3002,18 +2605,10 @@ __device__ __forceinline__ void item_cost_add(const DevScene& S, const WorkPlan&
 // loads became vector loads and the frames lost 5.5 %, profiles/r5/item_queue).  Every item
 // writes only its own sums: the frame does not depend on the assignment.  The kernels without
 // meshes keep blockIdx.x.
-#ifndef PTMI_ITEM_QUEUE
-#define PTMI_ITEM_QUEUE 1
-#endif
 __device__ __forceinline__ uint32_t take_item(uint32_t* __restrict__ ctr) {
-#if PTMI_ITEM_QUEUE
     uint32_t v = 0;
     if (threadIdx.x == 0) v = atomicAdd(ctr, 1u);
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);  // lane 0: every lane is active here
-#else
-    (void)ctr;
-    return blockIdx.x;
-#endif
 }
 // Lockstep item loop (kLockstepOf: the all-diffuse kernels without meshes).  The wave runs sample n of
 // its 64 pixels together: camera rays straight into registers, then at most kMaxEffectiveBounces
@@ -3054,12 +2649,8 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
     // colors (tracer.cl:1179) and the current path's accumColor: one LDS slot per lane each, as in
     // trace_kernel's regeneration loop (volatile: really in LDS, not promoted to VGPRs).
     __shared__ double acc_lds[3 * kBlock];
-#if PTMI_R6_VACC
     volatile __attribute__((address_space(3))) double* acc =
         (volatile __attribute__((address_space(3))) double*)(acc_lds + tid);
-#else
-    double* acc = acc_lds + tid;
-#endif
     acc[0 * kBlock] = 0.0;
     acc[1 * kBlock] = 0.0;
     acc[2 * kBlock] = 0.0;
@@ -3076,8 +2667,8 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
         PTMI_TSTAMP(t_a);
         bool alive = inside;
         if (alive) {
-            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
-            const DevCamera& cam = camera_ptr<(PTMI_CAM_RELOAD & 1) != 0>(S);
+            const DevScene& S = scene_reload(S0);
+            const DevCamera& cam = camera_ptr(S);
             PTMI_WADD(32, 1ull);
             d4 ro, rd;
             float rx, ry;
@@ -3090,7 +2681,6 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
             if constexpr ((FL & F_XRNG) != 0) P.rng = xseed(seed_bits, n);
         }
         PTMI_TADD(12, t_a);
-#if PTMI_STAGES
         // One bounce of the wave's live lanes at the wave-uniform index b.  kind: 0 -- the camera ray
         // (b == 0 at compile time; without DoF its origin terms come from the scene's tables), 1 -- a
         // middle bounce, 2 -- the last record: bounce_tail alone, no path state written.
@@ -3109,8 +2699,8 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
         };
         auto bounce = [&](auto kind, const uint32_t b) {
             constexpr int K = decltype(kind)::value;
-            constexpr int CAM = (K == 0 && !kDof && PTMI_CAM_TERMS) ? 1 : 0;
-            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
+            constexpr int CAM = (K == 0 && !kDof) ? 1 : 0;
+            const DevScene& S = scene_reload(S0);
             if (alive) {
                 PTMI_TSTAMP(t_b);
                 PTMI_WADD(45, 1ull);
@@ -3147,48 +2737,15 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
         for (uint32_t b = 1; b < kLast && __any(alive); b++) bounce(std::integral_constant<int, 1>(), b);
         if (__any(alive)) bounce(std::integral_constant<int, 2>(), kLast);
     }
-#else
-        for (uint32_t b = 0; __any(alive); b++) {
-            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
-            if (alive) {
-                PTMI_TSTAMP(t_b);
-                PTMI_WADD(45, 1ull);
-                PTMI_WADD(46, (unsigned long long)__popcll(__ballot(1)));
-                Hit h;
-                if (P.dead) h.pk = -1;
-                else h = find_closest_prims<FL>(S, P.ro, P.rd);
-                PTMI_TADD(13, t_b);
-                PTMI_TSTAMP(t_d);
-                // b is the path's bounce index and its effectiveBounces, for every lane alike.
-                P.b = P.effective = b;
-                bool ended = true;
-                if (b + 1 >= kMaxBounces || b + 1 >= kMaxEffectiveBounces)  // (wave-uniform) the last record
-                    bounce_tail(S, P, h, b, acm);
-                else
-                    ended = bounce_shade<FL, true, false, true>(S, P, h, fgi, n, acm);
-                if (ended) {
-                    acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
-                    acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
-                    acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
-                    // (F_MOM) bounce_tail's and bounce_shade's paths end in the same add
-                    if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
-                    alive = false;
-                }
-                PTMI_TADD(15, t_d);
-            }
-            PTMI_WADD(10, 1ull);
-        }
-    }
-#endif
     PTMI_TADD(16, t_loop);
 #if PTMI_STATS
     if (PTMI_FIRST_ACTIVE())
         for (int k = 0; k < 64; k++)
             if (ptmi_wstat[0][k]) atomicAdd(&ptmi_stats[k], ptmi_wstat[0][k]);
 #endif
-    store_sums<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
+    store_sums(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
                      acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
-    if constexpr (kMom) store_mom<true>(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
+    if constexpr (kMom) store_mom(work_item<kTilesOf<FL>>(S0, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
 }
 
 template <int FL>
@@ -3223,8 +2780,6 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
             ptmi_tl[2 * item + 1] = wall_clock64();
         }
 #endif
-    } else if constexpr (kPoolFlatOf<FL>) {
-        trace_flat_pool<FL>(S, samples, WP, seeds, sunf, sums, part, sq);
     } else if constexpr (kLockstepOf<FL>) {
         trace_lockstep<FL>(S, samples, WP, seeds, sunf, sums, part, sq);
 #if PTMI_TIMELINE
@@ -3255,12 +2810,8 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
         // volatile (round 6): without it the compiler, seeing no other reader, kept the three
         // sums in registers across the whole loop -- 6 VGPRs and 3 v_mov_b64 per iteration --
         // and wrote the LDS slots only after it.
-#if PTMI_R6_VACC
         volatile __attribute__((address_space(3))) double* acc =
             (volatile __attribute__((address_space(3))) double*)(acc_lds + tid);
-#else
-        double* acc = acc_lds + tid;
-#endif
         acc[0 * kBlock] = 0.0;
         acc[1 * kBlock] = 0.0;
         acc[2 * kBlock] = 0.0;
@@ -3292,13 +2843,13 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
         const DevScene& S0 = S;
         for (;;) {
             if (!__any(active || buffered || n_gen < c_end)) break;
-            const DevScene& S = scene_reload<(PTMI_SCENE_RELOAD & 2) != 0>(S0);
+            const DevScene& S = scene_reload(S0);
             PTMI_TSTAMP(t_a);
             const bool need = !buffered && n_gen < c_end;
             const int n_need = __popcll(__ballot(need));
             const int n_starve = __popcll(__ballot(!buffered && !active && n_gen < c_end));
             if (n_need >= kRefillNeed || n_starve >= PTMI_REFILL_STARVE || (n_starve > 0 && !__any(active))) {
-                const DevCamera& cam = camera_ptr<(PTMI_CAM_RELOAD & 1) != 0>(S);
+                const DevCamera& cam = camera_ptr(S);
                 PTMI_WADD(32, 1ull);
                 if (need) {
                     d4 ro, rd;
@@ -3331,7 +2882,7 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                     cro = mk(cbuf[3 * kWg], cbuf[4 * kWg], cbuf[5 * kWg], A ? 1.0 : cbuf[(kCamComp - 2) * kWg]);
                 else
                     {
-                    const double* co = camera_ptr<(PTMI_CAM_RELOAD & 1) != 0>(S).origin;  // ray_for_pixel's origin
+                    const double* co = camera_ptr(S).origin;  // ray_for_pixel's origin
                     cro = mk(co[0], co[1], co[2], 1.0);
                 }
                 start_path<A, (FL & F_DOF) != 0>(P, cro, crd);
@@ -3344,7 +2895,6 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                 active = true;
             }
             PTMI_TADD(12, t_a);
-#if PTMI_R6_LOOP
             // The hit lives only inside the active block (round 6): declared outside it, the
             // uninitialised Hit of inactive lanes became loop-carried registers, copied at every
             // iteration (6 v_mov_b64 per bounce).
@@ -3366,24 +2916,6 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
                 }
                 PTMI_TADD(15, t_d);
             }
-#else
-            PTMI_TSTAMP(t_b);
-            Hit h;
-            if (active) {
-                if (P.dead) h.pk = -1;
-                else h = find_closest_prims<FL>(S, P.ro, P.rd);
-            }
-            PTMI_TADD(13, t_b);
-            PTMI_TSTAMP(t_d);
-            if (active && bounce_shade<FL, true>(S, P, h, fgi, n_cur, acm)) {
-                acc[0 * kBlock] = acc[0 * kBlock] + acm[0 * kBlock];  // colors += accumColor (tracer.cl:1179)
-                acc[1 * kBlock] = acc[1 * kBlock] + acm[1 * kBlock];
-                acc[2 * kBlock] = acc[2 * kBlock] + acm[2 * kBlock];
-                if constexpr (kMom) m2[0] = m2[0] + mom_q(acm[0 * kBlock], acm[1 * kBlock], acm[2 * kBlock]);
-                active = false;
-            }
-            PTMI_TADD(15, t_d);
-#endif
             PTMI_WADD(10, 1ull);
         }
         PTMI_TADD(16, t_loop);
@@ -3392,9 +2924,9 @@ __global__ __launch_bounds__(kBlock, (FL & F_GROUPS)      ? PTMI_WAVES_GROUPS
             for (int k = 0; k < 64; k++)
                 if (ptmi_wstat[0][k]) atomicAdd(&ptmi_stats[k], ptmi_wstat[0][k]);
 #endif
-        store_sums<true>(work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
+        store_sums(work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane), WP, sums, part, acc[0 * kBlock], acc[1 * kBlock],
                    acc[2 * kBlock]);  // the work item re-derived: fewer live VGPRs
-        if constexpr (kMom) store_mom<true>(work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
+        if constexpr (kMom) store_mom(work_item<kTilesOf<FL>>(S, WP, blockIdx.x, lane), WP, sq, part, m2[0]);
 #if PTMI_TIMELINE
         if (threadIdx.x == 0 && blockIdx.x < ptmi_tl_max) {
             ptmi_tl[2 * blockIdx.x] = tl0;
@@ -3418,489 +2950,9 @@ static_assert(std::is_same<first_param<decltype(&trace_kernel<0>)>::type, DevSce
                   std::is_same<first_param<decltype(&trace_kernel<F_ALL>)>::type, DevScene>::value,
               "scene_reload: DevScene must be trace_kernel's first parameter (kernarg offset 0)");
 
-#if PTMI_STUDY
-// ==== STUDY build only (make study -> build/libptmi_study.so) ==========================
-// The standalone walk kernels and the split execution form of the mesh scenes are the
-// round-4 measurements behind DESIGN.md s5; they are not part of the product library.
-// ---- Standalone BVH walks (round 4) -------------------------------------------------
-// The mesh kernels walk inside their bounce loop, with the whole path state live: 4
-// waves/SIMD, and a walk phase runs ~24 parked lanes of 64 for as long as the longest
-// walk.  These kernels walk a list of requests (WalkReq: world ray + primitive best) with
-// nothing else live.  walk_kernel: one request per lane, the same group_walks code.
-// walk_pool_kernel: persistent waves, one walk step (a Node4 visit or a leaf) per lane per
-// iteration, and a lane whose walk ends takes the next request from a global counter, so
-// the wave's lanes stay busy to the end of the list.  Same candidate set, same
-// lexicographic minimum, same gate certification: the results equal group_walks'.
-#ifndef PTMI_WALK_WAVES
-#define PTMI_WALK_WAVES 5
-#endif
-template <bool A>
-__global__ __launch_bounds__(kBlock, PTMI_WALK_WAVES) void walk_kernel(DevScene S, const WalkReq* __restrict__ req,
-                                                                      uint32_t n, WalkRes* __restrict__ res) {
-    __shared__ int stk_lds[kStack * kStkStride];
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const WalkReq q = req[i];
-    Hit h{q.t, q.pk, -1, -1, 0.0, 0.0};
-    group_walks<A>(S, lds_ptr(stk_lds + threadIdx.x), mk(q.o[0], q.o[1], q.o[2], 1.0), mk(q.d[0], q.d[1], q.d[2], 0.0), h);
-    res[i] = WalkRes{h.t, h.pk, h.tri, h.ti, 0, h.u, h.v};
-}
-
-#ifndef PTMI_WALK_REFILL
-#define PTMI_WALK_REFILL 16  // lanes without a walk that trigger the wave's finish-and-refill step
-#endif
-template <bool A>
-__global__ __launch_bounds__(kBlock, PTMI_WALK_WAVES) void walk_pool_kernel(DevScene S,
-                                                                           const WalkReq* __restrict__ req,
-                                                                           uint32_t n, WalkRes* __restrict__ res,
-                                                                           uint32_t* __restrict__ next) {
-    __shared__ int stk_lds[kStack * kStkStride];
-    const int lane = threadIdx.x;
-    LdsInt* stk = lds_ptr(stk_lds + lane);
-    const int j_end = S.run_end[4];
-    // Lane phases: kIdle (no request), kWalk (walking object j of request ri), kDone (every
-    // object walked: the gate check, barycentrics and result store are pending), kDrained
-    // (the list is exhausted).  Finishing and refilling run for all such lanes of the wave
-    // together, once PTMI_WALK_REFILL of them wait (their FP64 work then runs on many
-    // lanes), or when no lane walks.
-    enum : int { kIdle = 0, kWalk = 1, kDone = 2, kDrained = 3 };
-    int phase = kIdle;
-    uint32_t ri = 0;
-    const int lb = S.leaf_bit;
-    int j = 0, cur = lb, sp = 0, vchain = -1;
-    bool cert = false;
-    d4 o = mk(0.0, 0.0, 0.0, 1.0), d = mk(0.0, 0.0, 0.0, 0.0);
-    WalkRay W{};
-    float lim = 0.0f;
-    Hit h{1024.0, -1, -1, -1, 0.0, 0.0};
-    // The walk of the first group object from jj on whose hull the segment [eps, best]
-    // can meet; kDone when none is left.
-    auto start_object = [&](int jj) {
-        const WalkReq& q = req[ri];
-        const d4 ro = mk(q.o[0], q.o[1], q.o[2], 1.0), rd = mk(q.d[0], q.d[1], q.d[2], 0.0);
-        for (; jj < j_end; jj++) {
-            const DevObject& ob = S.objs[jj];
-            o = xpt<A>(ob.inv, ob.st, ro);
-            d = xdir<A>(ob.inv, ob.st, rd);
-            const d4 r = mk(rcp_walk(d.x), rcp_walk(d.y), rcp_walk(d.z), 0.0);
-            const RootRec& R = S.root_rec[ob.child_base];  // one traversal index per group object
-            double tn;
-            if (cull_box(o, r, R.hull_mn[0], R.hull_mn[1], R.hull_mn[2], R.hull_mx[0], R.hull_mx[1], R.hull_mx[2],
-                         h.t + prune_margin(h.t), tn))
-                continue;
-            W = walk_setup(o, r, R);
-            lim = walk_limit(h.t);
-            cur = R.entry;
-            sp = 0;
-            vchain = -1;
-            break;
-        }
-        j = jj;
-        phase = jj < j_end ? kWalk : kDone;
-    };
-    for (;;) {
-        const uint64_t wait_m = __ballot(phase == kIdle || phase == kDone);
-        const bool any_walk = __any(phase == kWalk);
-        if (__popcll(wait_m) >= PTMI_WALK_REFILL || (wait_m != 0 && !any_walk)) {
-            if (phase == kDone) {  // the gate check (group_walks), barycentrics, result
-                const WalkReq& q = req[ri];
-                const d4 ro = mk(q.o[0], q.o[1], q.o[2], 1.0), rd = mk(q.d[0], q.d[1], q.d[2], 0.0);
-                if (h.tri >= 0 && !cert) {
-                    const DevObject& ob = S.objs[hit_obj(h)];
-                    if (!verify_chain(S, S.tris[h.ti].chain, xpt<A>(ob.inv, ob.st, ro), xdir<A>(ob.inv, ob.st, rd))) {
-                        h = Hit{q.t, q.pk, -1, -1, 0.0, 0.0};  // the eager walks
-                        group_walks_impl<A, true>(S, stk, ro, rd, h, cert);
-                    }
-                }
-                if (h.tri >= 0) {
-                    const DevObject& ob = S.objs[hit_obj(h)];
-                    tri_uv(S.tris[h.ti], xpt<A>(ob.inv, ob.st, ro), xdir<A>(ob.inv, ob.st, rd), h.u, h.v);
-                }
-                res[ri] = WalkRes{h.t, h.pk, h.tri, h.ti, 0, h.u, h.v};
-                phase = kIdle;
-            }
-            // refill: one atomic for the wave, each waiting lane takes the next request
-            const uint64_t im = __ballot(phase == kIdle);
-            const int first = __ffsll((long long)im) - 1;
-            uint32_t base = 0;
-            if (lane == first) base = atomicAdd(next, (uint32_t)__popcll(im));
-            base = __shfl(base, first);
-            if (phase == kIdle) {
-                ri = base + __popcll(im & ((1ull << lane) - 1));
-                if (ri < n) {
-                    const WalkReq& q = req[ri];
-                    h = Hit{q.t, q.pk, -1, -1, 0.0, 0.0};
-                    cert = false;
-                    start_object(S.run_end[3]);
-                } else {
-                    phase = kDrained;
-                }
-            }
-        }
-        if (!__any(phase == kWalk || phase == kDone)) break;
-        if (phase == kWalk) {  // one walk step of object j (walk_index's loop body)
-            bool down = false;
-            if (cur < lb) {
-                int nxt;
-                down = node_visit(S, stk, cur, sp, W, lim, nxt);
-                if (down) cur = nxt;
-            } else {
-                leaf_visit<false>(S, cur - lb, j, S.objs[j].key, o, d, h, vchain);
-                lim = walk_limit(h.t);
-            }
-            if (!down) {
-                if (sp > 0) {
-                    cur = stk[(--sp) * kStkStride];
-                } else {  // object j walked: certify a winner from it, then the next object
-                    if (h.tri >= 0 && hit_obj(h) == j) cert = chain_certified(S, S.tris[h.ti].chain, o, d, h.t);
-                    start_object(j + 1);
-                }
-            }
-        }
-    }
-}
-
-// ---- Split execution of mesh scenes (round 4) -------------------------------------
-// The mesh kernel above keeps every path in registers and walks the BVH in wave-wide walk
-// phases: ~24 parked lanes walk while the others wait, and parked lanes idle through the
-// primitive and shading phases.  Measured on the walks of real frames (tools/walk_bench.py,
-// profiles/r4/walk_kernel): the same walks cost 2.1x less in a standalone kernel, and the
-// mesh kernel without its walks (the mesh made invisible, hull culls kept) runs C4 / C5 in
-// 286 / 330 ms instead of 627 / 966 ms.  The split form runs those two halves as separate
-// kernels over a pool of path slots in HBM (SplitBufs), pass by pass:
-//   trace_split_kernel: each wave owns B.per_wave slots and hands them to its lanes; a lane
-//     resumes a slot's path (applying the walk result of the previous pass), traces it --
-//     primitives, hull culls, shading, its next samples -- until its ray needs a walk, then
-//     saves the path and the primitive best, appends the slot to the request list and takes
-//     the wave's next slot.  A slot whose pixel-chunk is finished claims the next one.
-//   walk_split_kernel: group_walks for every request of the pass (the same code as the mesh
-//     kernel's walk phases), result to the slot.
-// Per slot the samples of a pixel-chunk run in order with the reference's arithmetic, and
-// chunk sums go to the same partial records as the mesh kernel's chunk items, so the frame
-// equals a mesh-kernel render with the same chunk length bit for bit.
-#ifndef PTMI_WAVES_SPLIT
-#define PTMI_WAVES_SPLIT 4  // (round 5: 5 waves spilled 208 B/lane, the tracer pass then waited on memory 82 % of
-                            // its cycles; 4: 64 B/lane, C4 split frame 2444 -> 1511 ms, profiles/r5/split)
-#endif
-#ifndef PTMI_SPLIT_BATCH
-#define PTMI_SPLIT_BATCH 16  // waiting lanes that trigger a batched slot / claim / camera step
-#endif
-// A slot yields after starting B.budget samples in one pass (saved at a sample boundary,
-// resumed by the next pass): every wave then does about the same work per pass, so a pass
-// is not as long as its luckiest wave's run of walk-free samples.
-static constexpr uint32_t kFlagYield = 1u << 9;  // path flags: saved at a sample boundary, no walk pending
-// Pixel-chunks are claimed by the wave in blocks of one tile-chunk (64 consecutive ids, the
-// 64 pixels of one tile for one sample chunk), one global atomic per block.  (One atomic
-// per claim, and one per batch of walk requests, on shared counters had left the split
-// kernel's waves waiting on the atomic unit most of the pass.)
-static constexpr uint32_t kClaimBlock = 64;
-template <int FL>
-__global__ __launch_bounds__(kBlock, PTMI_WAVES_SPLIT) void trace_split_kernel(DevScene S, uint32_t samples,
-                                                                              WorkPlan WP, SplitBufs B,
-                                                                              const double* __restrict__ seeds,
-                                                                              const double* __restrict__ sunf,
-                                                                              double* __restrict__ part) {
-    static_assert((FL & F_GROUPS) && !(FL & (F_PROJ | F_TEX | F_XRNG)), "affine parity mesh scenes");
-    constexpr bool A = true;
-    constexpr bool kDof = (FL & F_DOF) != 0;
-    __shared__ double acc_lds[3 * kBlock];
-    const int lane = threadIdx.x;
-    double* acc = acc_lds + lane;
-    // The wave's next slot to hand out: wave-uniform, so every lane keeps its own copy and
-    // advances it by the same ballot count (a counter in LDS written by one lane and read
-    // by others without synchronisation had let lanes see stale values).
-    uint32_t next_slot = 0;
-    // Wave-uniform counters, kept identical in every lane: the claimed block of
-    // pixel-chunks [cl_next, cl_end), this pass's walk requests and yields.
-    uint32_t cl_next = B.wcl[2 * blockIdx.x], cl_end = B.wcl[2 * blockIdx.x + 1], n_req = 0, n_yield = 0;
-    bool claims_done = false;
-    const uint32_t L = B.L;
-    const uint32_t base = blockIdx.x * B.per_wave;
-    const uint32_t end = min(base + B.per_wave, L);
-    const int W = S.cam.width, H = S.cam.height;
-    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile;
-    const uint32_t n_tiles = max(WP.n_tail, 1u);
-    enum : int { kNoSlot = 0, kClaim = 1, kNeedCam = 2, kTrace = 3, kReady = 4, kExhausted = 5 };
-    int mode = kNoSlot;
-    uint32_t slot = 0, q = 0, n_cur = 0, c_end = 0, spent = 0;
-    int px = 0, py = 0;
-    float fgi = 0.0f;
-    PathState P;
-    start_path<A, kDof>(P, mk(0.0, 0.0, 0.0, 1.0), mk(0.0, 0.0, 0.0, 0.0));
-    Hit h{1024.0, -1, -1, -1, 0.0, 0.0};
-    // Pixel-chunk q -> pixel and sample range; false for a pixel outside the image.
-    auto decode = [&](uint32_t qq, uint32_t& c0) -> bool {
-        const uint32_t l = qq & 63u, tc = qq >> 6, c = tc / n_tiles, tk = tc - c * n_tiles;
-        const uint32_t tile = WP.tile_offset + tk * WP.tile_stride;
-        px = (int)(tile % (uint32_t)tiles_x) * kTile + (int)(l & 7u);
-        py = (int)(tile / (uint32_t)tiles_x) * kTile + (int)(l >> 3);
-        c0 = WP.s_begin + c * WP.chunk_len;
-        c_end = min(WP.s_end, c0 + WP.chunk_len);
-        return tile < (uint32_t)(tiles_x * tiles_y) && px < W && py < H;
-    };
-    auto R = [&]() -> SplitRec& { return reinterpret_cast<SplitRec*>(B.rec)[slot]; };
-    auto dget = [&](int k) -> double& { return R().d[k]; };
-    auto uget = [&](int k) -> uint32_t& { return R().u[k]; };
-    for (;;) {
-        const bool tr = mode == kTrace || mode == kReady;
-        // A. Lanes without a slot take the wave's next ones (batched).
-        {
-            const uint64_t m = __ballot(mode == kNoSlot);
-            if (m && (__popcll(m) >= PTMI_SPLIT_BATCH || !__any(tr || mode == kNeedCam || mode == kClaim))) {
-                const uint32_t b0 = next_slot;
-                next_slot += (uint32_t)__popcll(m);
-                if (mode == kNoSlot) {
-                    const uint32_t k = base + b0 + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-                    if (k >= end) {
-                        mode = kExhausted;
-                    } else {
-                        slot = k;
-                        const uint32_t it = uget(0);
-                        if (it == kSlotFree) {
-                            spent = 0;
-                            mode = kClaim;
-                        } else if (it != kSlotDead && (uget(2) & kFlagYield)) {  // yielded between samples
-                            q = it;
-                            uint32_t c0;
-                            decode(q, c0);
-                            n_cur = uget(1);
-                            acc[0 * kBlock] = dget(12), acc[1 * kBlock] = dget(13), acc[2 * kBlock] = dget(14);
-                            fgi = R().f[0];
-                            spent = 0;
-                            mode = kNeedCam;
-                        } else if (it != kSlotDead) {  // a path waiting for its walk result: resume it
-                            q = it;
-                            spent = 0;
-                            uint32_t c0;
-                            decode(q, c0);
-                            n_cur = uget(1);
-                            const uint32_t fl = uget(2);
-                            P.ro = mk(dget(0), dget(1), dget(2), 1.0);
-                            P.rd = mk(dget(3), dget(4), dget(5), 0.0);
-                            P.mr = dget(6), P.mg = dget(7), P.mb = dget(8);
-                            P.ar = dget(9), P.ag = dget(10), P.ab = dget(11);
-                            acc[0 * kBlock] = dget(12), acc[1 * kBlock] = dget(13), acc[2 * kBlock] = dget(14);
-                            P.b = fl & 15u, P.effective = (fl >> 4) & 7u;
-                            P.inside = (fl >> 7) & 1u, P.done = (fl >> 8) & 1u, P.dead = false;
-                            fgi = R().f[0];
-                            const WalkRes r = R().res;
-                            h = Hit{r.t, r.pk, r.tri, r.ti, r.u, r.v};
-                            mode = kReady;
-                        }
-                    }
-                }
-            }
-        }
-        // B. Slots without a pixel-chunk claim the next ones (batched, one atomic).
-        {
-            const uint64_t m = __ballot(mode == kClaim);
-            if (m && (__popcll(m) >= PTMI_SPLIT_BATCH || !__any(tr || mode == kNeedCam))) {
-                if (cl_next >= cl_end && !claims_done) {  // the wave's next block (one atomic)
-                    const int first = __ffsll((long long)m) - 1;
-                    uint32_t b0 = 0;
-                    if (lane == first) b0 = atomicAdd(&B.cnt[1], kClaimBlock);
-                    b0 = __shfl(b0, first);
-                    cl_next = b0;
-                    cl_end = min(b0 + kClaimBlock, B.n_items);
-                    claims_done = b0 >= B.n_items;
-                }
-                const uint32_t avail = cl_next < cl_end ? cl_end - cl_next : 0u;
-                const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1));
-                cl_next += min(avail, (uint32_t)__popcll(m));
-                if (mode == kClaim && rank >= avail) {
-                    if (claims_done) {  // every pixel-chunk is claimed: the slot is done for good
-                        uget(0) = kSlotDead;
-                        mode = kNoSlot;
-                    }  // else: claims again from the wave's next block
-                } else if (mode == kClaim) {
-                    const uint32_t qq = cl_next - min(avail, (uint32_t)__popcll(m)) + rank;
-                    {
-                        q = qq;
-                        uint32_t c0;
-                        if (!decode(q, c0)) {
-                            mode = kClaim;  // outside the image: nothing to render, claim again
-                        } else {
-                            uget(0) = q;
-                            n_cur = c0;
-                            acc[0 * kBlock] = 0.0, acc[1 * kBlock] = 0.0, acc[2 * kBlock] = 0.0;
-                            const double seed = seeds[(uint32_t)py * (uint32_t)W + (uint32_t)px];
-                            fgi = (float)(seed / (double)S.n_list);  // tracer.cl:840
-                            R().f[0] = fgi;
-                            R().f[1] = (float)(seed / (double)samples);  // fgi2, tracer.cl:841
-                            if (n_cur < c_end) {
-                                mode = kNeedCam;
-                            } else {  // an empty chunk (the range ends before it)
-                                double* o = part + (size_t)q * 4;
-                                o[0] = 0.0, o[1] = 0.0, o[2] = 0.0, o[3] = 0.0;
-                                uget(0) = kSlotFree;
-                                mode = kClaim;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        // C. Camera rays for the lanes starting a sample (batched: the camera block runs for
-        //    many lanes at once, as in the mesh kernel's refills).
-        {
-            const int n_cam = __popcll(__ballot(mode == kNeedCam));
-            if (n_cam && (n_cam >= PTMI_SPLIT_BATCH || !__any(tr))) {
-                n_yield += (uint32_t)__popcll(__ballot(mode == kNeedCam && spent >= B.budget));
-                if (mode == kNeedCam && spent >= B.budget) {  // yield: the next pass goes on from n_cur
-                    uget(1) = n_cur;
-                    uget(2) = kFlagYield;
-                    dget(12) = acc[0 * kBlock], dget(13) = acc[1 * kBlock], dget(14) = acc[2 * kBlock];
-                    mode = kNoSlot;
-                }
-                if (mode == kNeedCam) {
-                    spent++;
-                    const float fgi2 = R().f[1];
-                    float rx, ry;
-                    camera_offsets<FL>(fgi, fgi2, XSeed{}, n_cur, rx, ry);  // (parity mode only: no key)
-                    d4 ro, rd;
-                    ray_for_pixel<kDof, A>(camera_ptr(S), sunf, (unsigned)px, (unsigned)py, rx, ry, (int)n_cur, ro, rd);
-                    start_path<A, kDof>(P, ro, rd);
-                    mode = kTrace;
-                }
-            }
-        }
-        if (!__any(mode != kExhausted)) {
-            if (lane == 0) {
-                B.wcl[2 * blockIdx.x] = cl_next;
-                B.wcl[2 * blockIdx.x + 1] = cl_end;
-                B.seg[blockIdx.x] = n_req;
-                if (n_req) {
-                    atomicAdd(&B.cnt[0], n_req);
-                    atomicAdd(&B.cnt[3], n_req);  // all passes (diagnostics)
-                }
-                if (n_yield) atomicAdd(&B.cnt[2], n_yield);
-            }
-            break;
-        }
-        // D. Closest primitive; a ray whose segment can meet a mesh hull saves its path and
-        //    asks for a walk.
-        bool walk = false;
-        if (mode == kTrace) {
-            if (P.dead) {
-                h.pk = -1;
-                mode = kReady;
-            } else {
-                h = find_closest_prims<FL>(S, P.ro, P.rd);
-                if (group_needs_walk<A>(S, P.ro, P.rd, h)) {
-                    dget(0) = P.ro.x, dget(1) = P.ro.y, dget(2) = P.ro.z;
-                    dget(3) = P.rd.x, dget(4) = P.rd.y, dget(5) = P.rd.z;
-                    dget(6) = P.mr, dget(7) = P.mg, dget(8) = P.mb;
-                    dget(9) = P.ar, dget(10) = P.ag, dget(11) = P.ab;
-                    dget(12) = acc[0 * kBlock], dget(13) = acc[1 * kBlock], dget(14) = acc[2 * kBlock];
-                    dget(15) = h.t;
-                    uget(1) = n_cur;
-                    uget(2) = P.b | (P.effective << 4) | ((P.inside ? 1u : 0u) << 7) | ((P.done ? 1u : 0u) << 8);
-                    uget(3) = (uint32_t)h.pk;
-                    walk = true;
-                    mode = kNoSlot;
-                } else {
-                    mode = kReady;
-                }
-            }
-        }
-        {  // the walk requests of this step, appended to the wave's own segment
-            const uint64_t wm = __ballot(walk);
-            if (walk) B.req[base + n_req + (uint32_t)__popcll(wm & ((1ull << lane) - 1))] = slot;
-            n_req += (uint32_t)__popcll(wm);
-        }
-        // E. Shading (tracer.cl:886-1110); a finished path adds to the pixel-chunk's sums
-        //    (tracer.cl:1179), a finished chunk writes its record (r, g, b, samples).
-        if (mode == kReady) {
-            if (bounce_shade<FL>(S, P, h, fgi, n_cur)) {
-                acc[0 * kBlock] = acc[0 * kBlock] + P.ar;
-                acc[1 * kBlock] = acc[1 * kBlock] + P.ag;
-                acc[2 * kBlock] = acc[2 * kBlock] + P.ab;
-                n_cur++;
-                if (n_cur < c_end) {
-                    mode = kNeedCam;
-                } else {
-                    uint32_t c0;
-                    decode(q, c0);
-                    double* o = part + (size_t)q * 4;
-                    o[0] = acc[0 * kBlock], o[1] = acc[1 * kBlock], o[2] = acc[2 * kBlock];
-                    o[3] = (double)(c_end - c0);
-                    uget(0) = kSlotFree;
-                    mode = kClaim;
-                }
-            } else {
-                mode = kTrace;
-            }
-        }
-    }
-}
-
-// The walks of one split pass: every request appended by trace_split_kernel.
-__global__ __launch_bounds__(kBlock, PTMI_WALK_WAVES) void walk_split_kernel(DevScene S, SplitBufs B) {
-    __shared__ int stk_lds[kStack * kStkStride];
-    LdsInt* stk = lds_ptr(stk_lds + threadIdx.x);
-    const uint32_t nseg = (B.L + B.per_wave - 1) / B.per_wave;
-    for (uint32_t w = blockIdx.x; w < nseg; w += gridDim.x)  // tracer wave w's segment
-        for (uint32_t i = threadIdx.x, n = B.seg[w]; i - threadIdx.x < n; i += kBlock) {
-            if (i >= n) continue;
-            const uint32_t slot = B.req[(size_t)w * B.per_wave + i];
-            SplitRec& Rs = reinterpret_cast<SplitRec*>(B.rec)[slot];
-            const double* d = Rs.d;
-            Hit h{d[15], (int)Rs.u[3], -1, -1, 0.0, 0.0};
-            group_walks<true>(S, stk, mk(d[0], d[1], d[2], 1.0), mk(d[3], d[4], d[5], 0.0), h);
-            Rs.res = WalkRes{h.t, h.pk, h.tri, h.ti, 0, h.u, h.v};
-        }
-}
-
-bool split_supported(int flags) {
-    return (flags & F_GROUPS) && !(flags & (F_PROJ | F_TEX | F_XRNG | F_WIDE));
-}
-
-const void* trace_split_symbol(int flags) {
-    switch (flags & F_ALL) {
-#define K(f) \
-    case f: return reinterpret_cast<const void*>(&trace_split_kernel<f>);
-        K(1) K(3) K(5) K(7) K(9) K(11) K(13) K(15)
-#undef K
-    }
-    return nullptr;
-}
-const void* walk_split_symbol() { return reinterpret_cast<const void*>(&walk_split_kernel); }
-
-hipError_t launch_split_pass(const DevScene& S, int flags, uint32_t samples, const WorkPlan& WP, const SplitBufs& B,
-                             const double* seeds, const double* sunf, double* part, uint32_t walk_grid,
-                             hipStream_t st) {
-    if (!split_supported(flags)) return hipErrorInvalidValue;
-    const dim3 grid((B.L + B.per_wave - 1) / B.per_wave), block(kBlock);
-    switch (flags & F_ALL) {
-#define K(f)                                                                                                   \
-    case f:                                                                                                    \
-        hipLaunchKernelGGL(trace_split_kernel<f>, grid, block, 0, st, S, samples, WP, B, seeds, sunf, part); \
-        break;
-        K(1) K(3) K(5) K(7) K(9) K(11) K(13) K(15)
-#undef K
-    default:
-        return hipErrorInvalidValue;
-    }
-    hipLaunchKernelGGL(walk_split_kernel, dim3(walk_grid), block, 0, st, S, B);
-    return hipGetLastError();
-}
-
-hipError_t launch_walk(const DevScene& S, int flags, int mode, const WalkReq* req, uint32_t n, WalkRes* res,
-                       uint32_t* next, uint32_t grid, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    if ((flags & (F_PROJ | F_TEX | F_WIDE)) || !(flags & F_GROUPS)) return hipErrorInvalidValue;  // affine narrow-code mesh scenes
-    if (mode == 0) {
-        hipLaunchKernelGGL(walk_kernel<true>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, S, req, n, res);
-    } else {
-        hipLaunchKernelGGL(walk_pool_kernel<true>, dim3(grid), dim3(kBlock), 0, st, S, req, n, res, next);
-    }
-    return hipGetLastError();
-}
-
-const void* walk_kernel_symbol(int mode) {
-    return mode == 0 ? reinterpret_cast<const void*>(&walk_kernel<true>)
-                     : reinterpret_cast<const void*>(&walk_pool_kernel<true>);
-}
+#if PTMI_STUDY  // the standalone walk kernels and the split execution form
+#define PTMI_STUDY_PART 1
+#include "ptmi_study_kernels.h"
 #endif  // PTMI_STUDY
 
 #if PTMI_CAPTURE
@@ -4324,48 +3376,8 @@ hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream
 }
 
 #if PTMI_STUDY  // the measured tile order (needs PTMI_TILE_COST)
-// The next launch's dispatch order (WorkPlan::order) from the durations the last launch
-// measured (WorkPlan::cost): within the whole tiles and within the chunked tiles
-// separately, costliest first in 64 half-octave classes, any order within a class (the
-// order never changes a result); then the owned tiles' accumulators are cleared.  One
-// workgroup; a few microseconds.
-__global__ __launch_bounds__(1024) void tile_order_kernel(unsigned long long* __restrict__ cost, uint32_t n_whole,
-                                                           uint32_t n_tail, uint32_t stride, uint32_t offset,
-                                                           uint32_t* __restrict__ order) {
-    __shared__ uint32_t hist[2][64];
-    const uint32_t t = threadIdx.x, n = n_whole + n_tail;
-    if (t < 128) hist[t >> 6][t & 63] = 0;
-    __syncthreads();
-    auto cls = [&](uint32_t p) {
-        const unsigned long long c = cost[offset + p * stride];
-        const int l2 = 63 - __clzll(c | 1ull);              // floor(log2 c)
-        const int half = (c >> (l2 > 0 ? l2 - 1 : 0)) & 1;  // next bit: half octaves
-        return 63 - min(63, 2 * l2 + half);                 // costliest -> class 0
-    };
-    for (uint32_t p = t; p < n; p += blockDim.x) atomicAdd(&hist[p < n_whole ? 0 : 1][cls(p)], 1u);
-    __syncthreads();
-    if (t < 2) {
-        uint32_t run = t == 0 ? 0u : n_whole;
-        for (int b = 0; b < 64; b++) {
-            const uint32_t h = hist[t][b];
-            hist[t][b] = run;
-            run += h;
-        }
-    }
-    __syncthreads();
-    for (uint32_t p = t; p < n; p += blockDim.x) {
-        const bool w = p < n_whole;
-        order[atomicAdd(&hist[w ? 0 : 1][cls(p)], 1u)] = w ? p : p - n_whole;
-    }
-    __syncthreads();
-    for (uint32_t p = t; p < n; p += blockDim.x) cost[offset + p * stride] = 0ull;
-}
-
-hipError_t launch_tile_order(unsigned long long* cost, uint32_t n_whole, uint32_t n_tail, uint32_t stride,
-                             uint32_t offset, uint32_t* order, hipStream_t st) {
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, st, cost, n_whole, n_tail, stride, offset, order);
-    return hipGetLastError();
-}
+#define PTMI_STUDY_PART 2
+#include "ptmi_study_kernels.h"
 #endif  // PTMI_STUDY
 
 hipError_t launch_finalize(const double* sums, double* out, uint32_t npix, uint32_t samples, hipStream_t st) {

@@ -275,7 +275,7 @@ extern "C" int probe_ptmi_noise_sinf2_all(unsigned long long* mismatches, unsign
 }
 
 // v_fract_f32 (__builtin_amdgcn_fractf) against ocml's fract, min(x - floor(x), 0x1.fffffep-1), for
-// every finite float: whether noise3d may use the one instruction (PTMI_R6_FRACT).
+// every finite float: which is why noise3d uses the one instruction.
 __global__ void fract_check(uint64_t base, uint64_t count, unsigned long long* mism, unsigned int* first) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;

@@ -1,5 +1,5 @@
 """The lockstep item loop of the all-diffuse kernels without meshes (ptmi_kernels.hip
-trace_lockstep, PTMI_LOCKSTEP) against a kernel that keeps the regeneration loop and the full
+trace_lockstep) against a kernel that keeps the regeneration loop and the full
 shading on every bounce.
 
 The comparator is the material instantiation of the same scene, api.force_flags(4) (12 with

@@ -77,15 +77,12 @@ def test_kernel_noise_sinf_pair_bit_identical_all_floats():
 
 def test_fract_instruction_matches_ocml_fract_all_floats():
     """v_fract_f32 against ocml's fract (min(x - floor(x), 0x1.fffffep-1f)) on every finite float:
-    reported, and required only if the kernels use it (PTMI_R6_FRACT)."""
+    noise3d (ptmi_kernels.hip) takes its fract with the one instruction."""
     lib = _lib()
     m, f = ctypes.c_ulonglong(), ctypes.c_uint()
     assert lib.probe_fract_all(ctypes.byref(m), ctypes.byref(f)) == 0
     print("v_fract_f32 vs ocml fract: %d mismatches (first 0x%08x)" % (m.value, f.value))
-    import re
-    src = open(os.path.join(os.path.dirname(__file__), "..", "pathtracer-ocl_amd", "csrc", "ptmi_kernels.hip")).read()
-    if re.search(r"#define PTMI_R6_FRACT 1", src):
-        assert m.value == 0, "the kernels use v_fract_f32 but it differs from ocml's fract"
+    assert m.value == 0, "the kernels use v_fract_f32 but it differs from ocml's fract"
 
 
 def test_fp64_cores_match_compiler_operators():

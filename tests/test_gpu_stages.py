@@ -1,5 +1,5 @@
-"""The staged lockstep loop and the camera terms (ptmi_kernels.hip trace_lockstep, PTMI_STAGES /
-PTMI_CAM_TERMS; find_closest_prims' CAM form) against a kernel that has neither.
+"""The staged lockstep loop and the camera terms (ptmi_kernels.hip trace_lockstep;
+find_closest_prims' CAM form) against a kernel that has neither.
 
 The comparator is the one of test_gpu_lockstep: the same scene forced onto the material
 instantiation (api.force_flags), which keeps the regeneration loop and computes every origin term

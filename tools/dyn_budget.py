@@ -182,10 +182,10 @@ def prims_blocks(src_lines, fcp):
     if key in _blk_cache:
         return _blk_cache[key]
     marks = {"plane_ypair": "for (; p + 1 < npy; p += 2)", "plane_pair": "for (; p + 1 < np; p += 2)",
-             "plane_single": "if (p < np) {", "sphere_first_pair": "if (PTMI_R6_SPH && nq >= 2) {",
+             "plane_single": "if (p < np) {", "sphere_first_pair": "if (nq >= 2) {",
              "sphere_pair": "for (; q + 1 < nq; q += 2)", "sphere_single": "if (q < nq) {",
              "sphere_roots_call": "if (pend) {", "sphere_general": "for (; j < S.run_end[1]; j++) {",
-             "sphere_first_single": "if (PTMI_R6_SPH && nq == 1) {"}
+             "sphere_first_single": "if (nq == 1) {"}
     res = {}
     for i in range(fcp[0] - 1, fcp[1]):
         for name, m in marks.items():

@@ -8,8 +8,9 @@ Per segment it prints the instructions, the VGPR-to-VGPR v_mov_b64 and v_mov_b32
 consecutive v_mov_b64 copies (a copy of ro, rd and the mask is a run of nine), and scratch accesses.
 The path state is 64-bit, so its copies are the v_mov_b64 column; the v_mov_b32 copies are the noise
 arguments and the return values of normalize3, which every build has.  Last line: the kernel's
-instruction count, VGPRs and scratch bytes.  A build with the single bounce loop (-DPTMI_STAGES=0) has
-one find_closest_prims and so two segments; its loop-entry copies sit at the end of the first."""
+instruction count, VGPRs and scratch bytes.  A build of a revision with the single bounce loop (before
+the staged loop; tools/build_variant.sh FROMREV) has one find_closest_prims and so two segments; its
+loop-entry copies sit at the end of the first."""
 import re
 import sys
 

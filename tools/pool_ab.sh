@@ -10,5 +10,3 @@ for v in base nopool; do
   PTMI_LIB=$L timeout -k 10 300 python3 tools/shard_balance.py $OUT/shards_c4t_$v.json --configs c4 --worlds 8 --split tile > $OUT/shards_c4t_$v.log 2>&1
   grep -E "^c[0-9] " $OUT/shards_c4t_$v.log | sed "s/^/$v tile /"
 done
-# one-GPU frames with the pool in every affine mesh kernel (build/exp/libptmi_poolall.so, PTMI_POOL=2)
-bash tools/diag_ab.sh $OUT/ab 2048 "c4 c5" "base poolall base poolall"

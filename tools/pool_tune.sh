@@ -10,5 +10,3 @@ grep -E "^c[0-9] " $OUT/sh_old.log | sed "s/^/tailmin=32 /"
 bash tools/diag_ab.sh $OUT/ab 2048 "c4 c5" "base wb28 wb32 base wb28 wb32"
 timeout -k 10 200 python3 tools/wide_time.py 1280 960 64 > $OUT/wide_pool.txt 2>&1; tail -3 $OUT/wide_pool.txt
 PTMI_LIB=pathtracer-ocl_amd/build/exp/libptmi_nopool.so timeout -k 10 200 python3 tools/wide_time.py 1280 960 64 > $OUT/wide_nopool.txt 2>&1; tail -3 $OUT/wide_nopool.txt
-# the pool in the C2 kernel (PTMI_POOL_FLAT, non-DoF scenes without meshes) at 7 and 8 waves/SIMD
-bash tools/diag_ab.sh $OUT/ab2 2048 "c2" "base pf7 pf8 base pf7 pf8"
