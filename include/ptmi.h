@@ -264,6 +264,58 @@ int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width,
                    double* se_dev, double* tile_err_dev, double* stats_dev, void* hip_stream,
                    char* err, size_t err_len);
 
+/*
+ * First-hit feature buffers (an AOV pass): what the camera ray through each pixel's centre hits.
+ * feat_dev gets W*H*PTMI_FEATURE_DOUBLES doubles, row-major, one record per pixel:
+ *   [0..2] world position of the closest hit     [3] its t along the normalised ray direction
+ *   [4..6] world shading normal, unit, facing the eye (plane normal maps and interpolated
+ *          triangle normals included)            [7] the object's index in the caller's list
+ *                                                    as a double, -1.0 on a miss
+ *   [8..10] albedo: the object, triangle or texture colour the path's mask would be multiplied by
+ *          (an emissive object's colour too)     [11] 0.0
+ * The ray is the pinhole one (the aperture is ignored, so depth of field is not in these buffers),
+ * and the hit is the one the trace kernels pick for that ray, ties included.  Nothing here depends
+ * on seeds, sample counts or the RNG mode.  A miss writes id -1 and zeros elsewhere.  feat_dev must
+ * be 16-byte aligned.  Asynchronous on the stream.
+ */
+#define PTMI_FEATURE_DOUBLES 12
+int ptmi_scene_features(ptmi_scene* s, double* feat_dev, void* hip_stream, char* err, size_t err_len);
+
+/*
+ * A variance-guided, edge-avoiding a-trous wavelet filter (the spatial part of SVGF) over a frame:
+ *   rgba_dev  the frame (ptmi_finalize / ptmi_finalize_counts), W*H*4
+ *   se_dev    its standard-error map (ptmi_error_map), W*H: the filter's variance is se^2
+ *   feat_dev  the first-hit records (ptmi_scene_features)
+ * `iterations` passes with 5x5 B3-spline taps at distance 2^i; a tap's weight falls with the angle
+ * between the normals (cos^(2^normal_power)), with the tap's distance from the centre's tangent
+ * plane (sigma_d, relative to the hit's t) and with the luminance difference against the local
+ * standard deviation (sigma_l); hits and misses never mix.  With PTMI_DENOISE_DEMODULATE the colour
+ * is divided by max(albedo, 1e-3) before the passes and multiplied back after them, so texture detail
+ * is not blurred.  A pixel whose colour or se is not finite is copied through and read by no
+ * neighbour.  out_rgba_dev (W*H*4, A = 1.0) must not alias rgba_dev; out_se_dev (W*H, may be NULL)
+ * gets the filtered standard error.  The exact operation order is ptmi/denoise.py atrous_reference.
+ * work_dev: ptmi_denoise_work_bytes(W, H) bytes of scratch on the same device (two ping-pong
+ * states); work_dev, rgba_dev, feat_dev and out_rgba_dev must be 16-byte aligned.  Allocates
+ * nothing; asynchronous on the stream.  PTMI_ERR_ARG (and no launch) for NULL pointers, iterations
+ * outside 1..8, normal_power above 16, unknown flags, negative or non-finite sigmas, a short
+ * workspace or aliased frames.
+ */
+#define PTMI_DENOISE_DEMODULATE 1u
+typedef struct ptmi_denoise_params {
+    uint32_t iterations;   /* a-trous passes, step 2^i; default 5, 1..8 */
+    uint32_t flags;        /* PTMI_DENOISE_DEMODULATE = 1 (default on) */
+    double sigma_l;        /* luminance: default 4.0  */
+    double sigma_d;        /* plane distance, relative to the hit's t: default 0.01 */
+    uint32_t normal_power; /* w_n = max(0, n_p.n_q)^(2^k), k = normal_power: default 7 (exponent 128) */
+    uint32_t reserved;
+} ptmi_denoise_params;
+
+size_t ptmi_denoise_work_bytes(uint32_t width, uint32_t height);
+int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* feat_dev, uint32_t width,
+                 uint32_t height, const ptmi_denoise_params* params /* NULL = defaults */, double* out_rgba_dev,
+                 double* out_se_dev /* may be NULL */, void* work_dev, size_t work_bytes, void* hip_stream,
+                 char* err, size_t err_len);
+
 /* dst_dev[k] += src_dev[k] over n doubles, on the caller's stream: batches of sums
  * (A included, so the sample counts add) and of second moments. */
 int ptmi_accumulate(double* dst_dev, const double* src_dev, size_t n, void* hip_stream, char* err,

@@ -99,6 +99,12 @@ int ptmi_diag_scene_flags(const ptmi_scene* s);
  * to rank (x + y) mod stride), 0 raster (tile t to rank t mod stride); -1 for bad arguments. */
 int ptmi_diag_tile_ownership(const ptmi_scene* s, uint32_t tile_stride);
 
+/* Which form of the a-trous pass ptmi_denoise launches, process-wide: 0 every pass gathers its taps
+ * from global memory, 1 the passes at steps 1 and 2 stage the block's pixels and halo in LDS first.
+ * Both give the same bits; the library's default is the measured faster one
+ * (profiles/denoise/SUMMARY.md).  Returns the previous value, or -1 for an unknown form. */
+int ptmi_diag_denoise_variant(int variant);
+
 #ifdef __cplusplus
 }
 #endif

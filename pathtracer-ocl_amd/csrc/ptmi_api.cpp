@@ -51,6 +51,10 @@ hipError_t launch_camera_terms(const DevScene& S, hipStream_t st);
 hipError_t launch_hemi_table(double* out, int* mismatch, hipStream_t st);
 hipError_t launch_combine(const double* parts, uint32_t nparts, size_t npix, double* out, uint32_t samples,
                           hipStream_t st);
+hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st);
+hipError_t launch_denoise(const double* rgba, const double* se, const double* feat, uint32_t W, uint32_t H,
+                          uint32_t iterations, bool demod, double sigma_l, double sigma_d, uint32_t npow, double* out,
+                          double* out_se, double* work, int variant, hipStream_t st);
 const void* trace_kernel_symbol(int flags);
 bool tile_list_supported(int flags);
 int trace_kernel_flags(int flags);
@@ -144,6 +148,8 @@ struct ptmi_scene {
 // ptmi_diag_force_flags: kernel flags forced onto every scene created after the call
 // (-1: none).  Test hook for the generic instantiations.
 static std::atomic<int> g_force_flags{-1};
+// ptmi_diag_denoise_variant: the form of the a-trous pass (ptmi_kernels.hip launch_denoise).
+static std::atomic<int> g_denoise_variant{1};  // the LDS form: 2.20 against 3.01 ms (profiles/denoise/SUMMARY.md)
 
 namespace {
 
@@ -1319,6 +1325,52 @@ int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width,
     return PTMI_OK;
 }
 
+int ptmi_scene_features(ptmi_scene* s, double* feat_dev, void* hip_stream, char* err, size_t err_len) {
+    if (!s || !feat_dev || ((uintptr_t)feat_dev & 15u)) {
+        set_err(err, err_len, "bad feature-pass arguments");
+        return PTMI_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_features(s->dev, feat_dev, (hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
+size_t ptmi_denoise_work_bytes(uint32_t width, uint32_t height) {
+    return (size_t)width * (size_t)height * 2 * 4 * sizeof(double);  // two (r, g, b, var) states
+}
+
+int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* feat_dev, uint32_t width, uint32_t height,
+                 const ptmi_denoise_params* params, double* out_rgba_dev, double* out_se_dev, void* work_dev,
+                 size_t work_bytes, void* hip_stream, char* err, size_t err_len) {
+    ptmi_denoise_params p{5, PTMI_DENOISE_DEMODULATE, 4.0, 0.01, 7, 0};
+    if (params) p = *params;
+    if (!rgba_dev || !se_dev || !feat_dev || !out_rgba_dev || !work_dev || width == 0 || height == 0 ||
+        width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
+        set_err(err, err_len, "bad denoise arguments (%u x %u)", width, height);
+        return PTMI_ERR_ARG;
+    }
+    if (p.iterations < 1 || p.iterations > 8 || (p.flags & ~PTMI_DENOISE_DEMODULATE) || p.normal_power > 16 ||
+        !(std::isfinite(p.sigma_l) && p.sigma_l >= 0.0 && std::isfinite(p.sigma_d) && p.sigma_d >= 0.0)) {
+        set_err(err, err_len, "bad denoise parameters (iterations %u flags %u sigma_l %g sigma_d %g normal_power %u)",
+                p.iterations, p.flags, p.sigma_l, p.sigma_d, p.normal_power);
+        return PTMI_ERR_ARG;
+    }
+    if (work_bytes < ptmi_denoise_work_bytes(width, height)) {
+        set_err(err, err_len, "denoise workspace of %zu bytes, %zu needed", work_bytes,
+                ptmi_denoise_work_bytes(width, height));
+        return PTMI_ERR_ARG;
+    }
+    if (out_rgba_dev == rgba_dev || (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)out_rgba_dev |
+                                      (uintptr_t)work_dev) & 15u)) {
+        set_err(err, err_len, "denoise buffers aliased or not 16-byte aligned");
+        return PTMI_ERR_ARG;
+    }
+    const bool demod = (p.flags & PTMI_DENOISE_DEMODULATE) != 0;  // (outside HIP_TRY: its message quotes the call)
+    HIP_TRY(launch_denoise(rgba_dev, se_dev, feat_dev, width, height, p.iterations, demod, p.sigma_l, p.sigma_d, p.normal_power, out_rgba_dev,
+                           out_se_dev, (double*)work_dev, g_denoise_variant.load(), (hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
 int ptmi_accumulate(double* dst_dev, const double* src_dev, size_t n, void* hip_stream, char* err, size_t err_len) {
     if (!dst_dev || !src_dev) {
         set_err(err, err_len, "bad accumulate arguments");
@@ -1803,6 +1855,11 @@ extern "C" int ptmi_diag_force_flags(int flags) {
     if (flags > 63) return PTMI_ERR_ARG;
     g_force_flags.store(flags < 0 ? -1 : flags);
     return PTMI_OK;
+}
+
+extern "C" int ptmi_diag_denoise_variant(int variant) {
+    if (variant < 0 || variant > 1) return -1;
+    return g_denoise_variant.exchange(variant);
 }
 
 extern "C" int ptmi_diag_hemi_mismatch(const ptmi_scene* s) { return s ? s->hemi_mismatch : -1; }

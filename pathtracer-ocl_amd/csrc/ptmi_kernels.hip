@@ -3033,6 +3033,313 @@ hipError_t launch_camera_terms(const DevScene& S, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---- First-hit features (ptmi_scene_features) ----------------------------------------------
+// What the pinhole ray through each pixel's centre hits: one lane per pixel on 8x8 tiles, 12 doubles
+// per pixel (include/ptmi.h).  The hit is the trace kernels' -- find_closest_prims, then group_walks
+// with its gate chain -- in the one generic instantiation (double4 arithmetic, 32-bit LDS stack,
+// texture lookups), which gives the affine forms' bits.  The normal and the colour restate the head
+// of bounce_shade and its bounce record (tracer.cl:903-955, 1071-1092) rather than share helpers with
+// it: one ray per pixel, and the trace kernels keep their ISA.
+static constexpr int kFeatFL = F_ALL | F_PROJ | F_TEX;
+__global__ __launch_bounds__(kBlock) void scene_features(DevScene S, double* __restrict__ feat) {
+    constexpr bool A = false;
+    __shared__ int stk_lds[kStack * kStkStride];
+    const int t = threadIdx.x, W = S.cam.width, H = S.cam.height, tiles_x = (W + kTile - 1) / kTile;
+    const int px = (int)(blockIdx.x % (uint32_t)tiles_x) * kTile + (t & 7);
+    const int py = (int)(blockIdx.x / (uint32_t)tiles_x) * kTile + (t >> 3);
+    if (px >= W || py >= H) return;
+    d4 ro, rd;
+    ray_for_pixel<false, A>(S.cam, nullptr, (unsigned)px, (unsigned)py, 0.5f, 0.5f, 0, ro, rd);
+    Hit h = find_closest_prims<kFeatFL>(S, ro, rd);
+    if (S.run_end[4] > S.run_end[3]) group_walks<A>(S, lds_ptr(stk_lds + t), ro, rd, h);
+    double2* o = reinterpret_cast<double2*>(feat + 12 * ((size_t)py * W + px));
+    if (h.pk < 0) {
+        o[0] = o[1] = o[2] = o[4] = o[5] = make_double2(0.0, 0.0);
+        o[3] = make_double2(0.0, -1.0);
+        return;
+    }
+    const DevObject& ob = S.objs[h.pk & 0xFFFF];
+    const int type = ob.type;
+    const d4 pos = add4(ro, scl4(rd, h.t));
+    const d4 eye = mk(-rd.x, -rd.y, -rd.z, -rd.w);
+    // Object normal -> world normal (bounce_shade; tracer.cl:903-955).
+    d4 nv;
+    if (type == 0 && !ob.tex_nm) {
+        nv = ld4(ob.plane_n);
+    } else {
+        d4 on;
+        if (type == 0) {
+            on = plane_normal_map<A>(S.tex[0], ob, pos);
+        } else if (type == 1) {
+            const d4 lp = xpt<A>(ob.inv, ob.st, pos);
+            on = mk(lp.x - 0.0, lp.y - 0.0, lp.z - 0.0, lp.w - 1.0);
+        } else if (type == 2) {
+            const d4 lp = xpt<A>(ob.inv, ob.st, pos);
+            const double dist = lp.x * lp.x + lp.z * lp.z;
+            if (dist < 1 && lp.y >= ob.max_y - kEps) on = mk(0.0, 1.0, 0.0, 0.0);
+            else if (dist < 1 && lp.y <= ob.min_y + kEps) on = mk(0.0, -1.0, 0.0, 0.0);
+            else on = mk(lp.x, 0.0, lp.z, 0.0);
+        } else if (type == 3) {
+            const d4 lp = xpt<A>(ob.inv, ob.st, pos);
+            const double mc = max3(fabs(lp.x), fabs(lp.y), fabs(lp.z));
+            if (mc == fabs(lp.x)) on = mk(lp.x, 0.0, 0.0, 0.0);
+            else if (mc == fabs(lp.y)) on = mk(0.0, lp.y, 0.0, 0.0);
+            else on = mk(0.0, 0.0, lp.z, 0.0);
+        } else {
+            const DevTriShade& T = S.tri_shade[h.tri];
+            on = add4(add4(scl4(ld4(T.n2), h.u), scl4(ld4(T.n3), h.v)), scl4(ld4(T.n1), 1.0 - h.u - h.v));
+        }
+        const double* it = ob.inv_t;
+        if (ob.invt_diag) {
+            nv = mk(it[0] * on.x, it[5] * on.y, it[10] * on.z, 0.0);
+        } else {
+            nv.x = ((it[0] * on.x + it[1] * on.y) + it[2] * on.z) + it[3] * on.w;
+            nv.y = ((it[4] * on.x + it[5] * on.y) + it[6] * on.z) + it[7] * on.w;
+            nv.z = ((it[8] * on.x + it[9] * on.y) + it[10] * on.z) + it[11] * on.w;
+            nv.w = 0.0;
+        }
+        nv = normv<A>(nv);
+    }
+    if (dotv<A>(eye, nv) < 0.0) nv = scl4(nv, -1.0);
+    // The colour of the bounce record (tracer.cl:1071-1092): an emissive hit keeps its colour too.
+    double cr, cg, cb;
+    if (type == 4) {
+        const DevTriShade& T = S.tri_shade[h.tri];
+        cr = T.color[0], cg = T.color[1], cb = T.color[2];
+    } else {
+        cr = ob.color[0], cg = ob.color[1], cb = ob.color[2];
+        if (ob.tex) textured_color<A>(S.tex[type == 0 ? 0 : type == 1 ? 1 : 2], ob, pos, cr, cg, cb);
+    }
+    o[0] = make_double2(pos.x, pos.y);
+    o[1] = make_double2(pos.z, h.t);
+    o[2] = make_double2(nv.x, nv.y);
+    o[3] = make_double2(nv.z, (double)ob.key);
+    o[4] = make_double2(cr, cg);
+    o[5] = make_double2(cb, 0.0);
+}
+
+hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st) {
+    const uint32_t tiles = (uint32_t)((S.cam.width + kTile - 1) / kTile) * (uint32_t)((S.cam.height + kTile - 1) / kTile);
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(scene_features, dim3(tiles), dim3(kBlock), 0, st, S, feat);
+    return hipGetLastError();
+}
+
+// ---- The a-trous denoiser (ptmi_denoise) ------------------------------------------------------
+// An edge-avoiding wavelet filter steered by the first-hit records and the pixels' variance.  The
+// state is (r, g, b, var) per pixel, ping-ponged between the two halves of the caller's workspace:
+// denoise_start forms it, denoise_pass runs once per step 2^i, denoise_end writes the frame.  Every
+// FP64 operation is separately rounded and in the order ptmi/denoise.py atrous_reference states;
+// exp is the one operation numpy may round differently.
+struct DenoiseArgs {
+    int W, H, step, npow;
+    double sigma_l, sigma_d;
+};
+// A tap: its state, and of its record the position, the normal and the object id.
+struct DnTap {
+    double c0, c1, c2, v, x0, x1, x2, n0, n1, n2, id;
+};
+__device__ __forceinline__ double dn_lum(double r, double g, double b) { return (0.2126 * r + 0.7152 * g) + 0.0722 * b; }
+__device__ __forceinline__ double dn_floor(double a) { return a > 1e-3 ? a : 1e-3; }  // (NaN: the floor)
+__device__ __forceinline__ bool dn_finite(double a, double b, double c, double d) {
+    return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);
+}
+
+__global__ __launch_bounds__(256) void denoise_start(const double* __restrict__ rgba, const double* __restrict__ se,
+                                                     const double* __restrict__ feat, double* __restrict__ state,
+                                                     uint32_t npix, bool demod) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const double2* p = reinterpret_cast<const double2*>(rgba + 4 * (size_t)i);
+    const double2* f = reinterpret_cast<const double2*>(feat + 12 * (size_t)i);
+    const double2 p0 = p[0], p1 = p[1], a0 = f[4], a1 = f[5];
+    const double s = se[i];
+    double r = p0.x, g = p0.y, b = p1.x, v = s * s;
+    if (demod) {
+        const double m = dn_floor(dn_lum(a0.x, a0.y, a1.x));
+        r = r / dn_floor(a0.x);
+        g = g / dn_floor(a0.y);
+        b = b / dn_floor(a1.x);
+        v = v / (m * m);
+    }
+    double2* o = reinterpret_cast<double2*>(state + 4 * (size_t)i);
+    o[0] = make_double2(r, g);
+    o[1] = make_double2(b, v);
+}
+
+__global__ __launch_bounds__(256) void denoise_end(const double* __restrict__ state, const double* __restrict__ rgba,
+                                                   const double* __restrict__ se, const double* __restrict__ feat,
+                                                   double* __restrict__ out, double* __restrict__ out_se, uint32_t npix,
+                                                   bool demod) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const double2* p = reinterpret_cast<const double2*>(rgba + 4 * (size_t)i);
+    const double2* q = reinterpret_cast<const double2*>(state + 4 * (size_t)i);
+    const double2* f = reinterpret_cast<const double2*>(feat + 12 * (size_t)i);
+    const double2 p0 = p[0], p1 = p[1], q0 = q[0], q1 = q[1], a0 = f[4], a1 = f[5];
+    const double s = se[i];
+    double r = q0.x, g = q0.y, b = q1.x, e = sqrt(q1.y);
+    if (demod) {
+        r = r * dn_floor(a0.x);
+        g = g * dn_floor(a0.y);
+        b = b * dn_floor(a1.x);
+        e = e * dn_floor(dn_lum(a0.x, a0.y, a1.x));
+    }
+    if (!dn_finite(p0.x, p0.y, p1.x, s)) r = p0.x, g = p0.y, b = p1.x, e = s;  // such a pixel passes through
+    double2* o = reinterpret_cast<double2*>(out + 4 * (size_t)i);
+    o[0] = make_double2(r, g);
+    o[1] = make_double2(b, 1.0);
+    if (out_se) out_se[i] = e;
+}
+
+// One pass, one thread per pixel on kDnX x kDnY blocks.  kLdsStep == 0: every tap is a global gather
+// (two 16-B loads of state, four of the record).  kLdsStep == 1, 2: the pass at that step with the
+// block's pixels and their halo of 2 * step staged in LDS first, 11 planes of doubles; the arithmetic
+// is the same, so the two forms give the same bits.
+static constexpr int kDnX = 16, kDnY = 16;
+template <int kLdsStep>
+__global__ __launch_bounds__(kDnX * kDnY) void denoise_pass(const double* __restrict__ sin,
+                                                            const double* __restrict__ feat,
+                                                            double* __restrict__ sout, DenoiseArgs a) {
+    constexpr bool kLds = kLdsStep != 0;
+    constexpr int kHalo = 2 * kLdsStep, kTW = kDnX + 2 * kHalo, kTH = kDnY + 2 * kHalo;
+    __shared__ double lds[kLds ? 11 : 1][kLds ? kTW * kTH : 1];
+    const int W = a.W, H = a.H, step = kLds ? kLdsStep : a.step;
+    const int bx0 = (int)blockIdx.x * kDnX, by0 = (int)blockIdx.y * kDnY;
+    const int x = bx0 + (int)threadIdx.x % kDnX, y = by0 + (int)threadIdx.x / kDnX;
+    auto gtap = [&](int qx, int qy) {
+        const size_t i = (size_t)qy * W + qx;
+        const double2* s = reinterpret_cast<const double2*>(sin + 4 * i);
+        const double2* f = reinterpret_cast<const double2*>(feat + 12 * i);
+        const double2 s0 = s[0], s1 = s[1], f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
+        return DnTap{s0.x, s0.y, s1.x, s1.y, f0.x, f0.y, f1.x, f2.x, f2.y, f3.x, f3.y};
+    };
+    if constexpr (kLds) {  // in-image pixels of the tile; the others are never read (their taps are skipped)
+        for (int k = (int)threadIdx.x; k < kTW * kTH; k += kDnX * kDnY) {
+            const int qx = bx0 - kHalo + k % kTW, qy = by0 - kHalo + k / kTW;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const DnTap T = gtap(qx, qy);
+            lds[0][k] = T.c0, lds[1][k] = T.c1, lds[2][k] = T.c2, lds[3][k] = T.v;
+            lds[4][k] = T.x0, lds[5][k] = T.x1, lds[6][k] = T.x2;
+            lds[7][k] = T.n0, lds[8][k] = T.n1, lds[9][k] = T.n2, lds[10][k] = T.id;
+        }
+        __syncthreads();
+    }
+    if (x >= W || y >= H) return;
+    auto tap = [&](int qx, int qy) {
+        if constexpr (kLds) {
+            const int k = (qy - by0 + kHalo) * kTW + (qx - bx0 + kHalo);
+            return DnTap{lds[0][k], lds[1][k], lds[2][k], lds[3][k], lds[4][k], lds[5][k],
+                         lds[6][k], lds[7][k], lds[8][k], lds[9][k], lds[10][k]};
+        } else {
+            return gtap(qx, qy);
+        }
+    };
+    // the state and the id alone (the variance prefilter's taps)
+    auto tap_s = [&](int qx, int qy) {
+        if constexpr (kLds) {
+            const int k = (qy - by0 + kHalo) * kTW + (qx - bx0 + kHalo);
+            return DnTap{lds[0][k], lds[1][k], lds[2][k], lds[3][k], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, lds[10][k]};
+        } else {
+            const size_t i = (size_t)qy * W + qx;
+            const double2* s = reinterpret_cast<const double2*>(sin + 4 * i);
+            const double2 s0 = s[0], s1 = s[1];
+            return DnTap{s0.x, s0.y, s1.x, s1.y, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, feat[12 * i + 7]};
+        }
+    };
+    const size_t i = (size_t)y * W + x;
+    const DnTap P = tap(x, y);
+    double2* o = reinterpret_cast<double2*>(sout + 4 * i);
+    if (!dn_finite(P.c0, P.c1, P.c2, P.v)) {  // passes through
+        o[0] = make_double2(P.c0, P.c1);
+        o[1] = make_double2(P.c2, P.v);
+        return;
+    }
+    const bool miss = P.id < 0.0;
+    // the variance around p: 3x3 (1/4, 1/8, 1/16) at distance 1 over the taps the filter itself would take
+    double sv = 0.0, sk = 0.0;
+#pragma unroll
+    for (int gy = 0; gy < 3; gy++) {
+#pragma unroll
+        for (int gx = 0; gx < 3; gx++) {
+            const double k = (gx == 1 ? 0.5 : 0.25) * (gy == 1 ? 0.5 : 0.25);
+            const int qx = x + gx - 1, qy = y + gy - 1;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const DnTap Q = tap_s(qx, qy);
+            if (!dn_finite(Q.c0, Q.c1, Q.c2, Q.v) || (Q.id < 0.0) != miss) continue;
+            sv = sv + k * Q.v;
+            sk = sk + k;
+        }
+    }
+    const double vbar = sv / sk;
+    const double sd = a.sigma_l * sqrt(vbar < 0.0 ? 0.0 : vbar) + 1e-12;
+    const double dd_den = a.sigma_d * feat[12 * i + 3] + 1e-12;
+    const double lp = dn_lum(P.c0, P.c1, P.c2);
+    double sw = 0.0, s2 = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0;
+#pragma unroll
+    for (int iy = 0; iy < 5; iy++) {
+#pragma unroll
+        for (int ix = 0; ix < 5; ix++) {
+            const double hx = ix == 2 ? 0.375 : (ix == 1 || ix == 3) ? 0.25 : 0.0625;
+            const double hy = iy == 2 ? 0.375 : (iy == 1 || iy == 3) ? 0.25 : 0.0625;
+            const double hh = hx * hy;
+            const int qx = x + (ix - 2) * step, qy = y + (iy - 2) * step;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const DnTap Q = tap(qx, qy);
+            if (!dn_finite(Q.c0, Q.c1, Q.c2, Q.v) || (Q.id < 0.0) != miss) continue;
+            double w = hh;
+            if (!(ix == 2 && iy == 2)) {
+                const double wl = exp(-(fabs(lp - dn_lum(Q.c0, Q.c1, Q.c2)) / sd));
+                if (miss) {
+                    w = hh * wl;
+                } else {
+                    const double dn = (P.n0 * Q.n0 + P.n1 * Q.n1) + P.n2 * Q.n2;
+                    double wn = dn > 0.0 ? dn : 0.0;
+                    for (int k = 0; k < a.npow; k++) wn = wn * wn;
+                    const double dd = (P.n0 * (Q.x0 - P.x0) + P.n1 * (Q.x1 - P.x1)) + P.n2 * (Q.x2 - P.x2);
+                    const double wd = exp(-(fabs(dd) / dd_den));
+                    w = ((hh * wn) * wd) * wl;
+                }
+            }
+            sw = sw + w;
+            s2 = s2 + (w * w) * Q.v;
+            r0 = r0 + w * (Q.c0 - P.c0);
+            r1 = r1 + w * (Q.c1 - P.c1);
+            r2 = r2 + w * (Q.c2 - P.c2);
+        }
+    }
+    // the weighted mean written around c_p: equal colours stay equal bit for bit
+    o[0] = make_double2(P.c0 + r0 / sw, P.c1 + r1 / sw);
+    o[1] = make_double2(P.c2 + r2 / sw, s2 / (sw * sw));
+}
+
+// work: two states of npix * 4 doubles.  variant (ptmi_diag_denoise_variant): 0 every pass gathers from
+// global memory; 1 the passes at steps 1 and 2 stage their tile in LDS.
+hipError_t launch_denoise(const double* rgba, const double* se, const double* feat, uint32_t W, uint32_t H,
+                          uint32_t iterations, bool demod, double sigma_l, double sigma_d, uint32_t npow, double* out,
+                          double* out_se, double* work, int variant, hipStream_t st) {
+    const uint32_t npix = W * H;
+    double* cur = work;
+    double* nxt = work + 4 * (size_t)npix;
+    hipLaunchKernelGGL(denoise_start, dim3((npix + 255) / 256), dim3(256), 0, st, rgba, se, feat, cur, npix, demod);
+    const dim3 grid((W + kDnX - 1) / kDnX, (H + kDnY - 1) / kDnY), block(kDnX * kDnY);
+    for (uint32_t i = 0; i < iterations; i++) {
+        const DenoiseArgs a{(int)W, (int)H, 1 << i, (int)npow, sigma_l, sigma_d};
+        if (variant == 1 && i == 0)
+            hipLaunchKernelGGL(denoise_pass<1>, grid, block, 0, st, cur, feat, nxt, a);
+        else if (variant == 1 && i == 1)
+            hipLaunchKernelGGL(denoise_pass<2>, grid, block, 0, st, cur, feat, nxt, a);
+        else
+            hipLaunchKernelGGL(denoise_pass<0>, grid, block, 0, st, cur, feat, nxt, a);
+        double* tmp = cur;
+        cur = nxt;
+        nxt = tmp;
+    }
+    hipLaunchKernelGGL(denoise_end, dim3((npix + 255) / 256), dim3(256), 0, st, cur, rgba, se, feat, out, out_se, npix,
+                       demod);
+    return hipGetLastError();
+}
+
 // The tail tiles' chunk partials (WorkPlan) summed in chunk order (deterministic)
 // into the frame; one thread per tail-tile pixel.  kMom (moment renders): the chunk items' second
 // moments (store_mom's plane) summed in chunk order likewise, into sq.

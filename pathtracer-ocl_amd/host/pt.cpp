@@ -22,6 +22,11 @@
 // ptmi_scene_render_tiles, ptmi_select_tiles, ptmi_finalize_counts); samples_done is then the
 // largest per-tile count, and a second line gives the mean samples per pixel and the tiles that
 // ran to --samples.  --sample-map FILE writes the per-pixel sample counts as a .raw image.
+// --denoise (one GPU) filters the frame before the PNG / raw writers (ptmi_scene_features, ptmi_denoise
+// with the library's default parameters; --denoise-iters N sets the number of a-trous passes, 1..8).
+// Alone it renders every sample with moments, in batches of --batch; with --noise-target or --adaptive
+// it filters the frame those loops stop at, and --error-map then holds the filtered standard error.
+// --features FILE writes the first-hit normals as a .raw image (RGB = n * 0.5 + 0.5).
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
 #include <algorithm>
 #include <chrono>
@@ -53,6 +58,9 @@ struct Cfg {
     std::string error_map;
     bool adaptive = false;
     std::string sample_map;
+    bool denoise = false, have_iters = false;
+    int denoise_iters = 0;  // 0: the library's default
+    std::string features;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -61,7 +69,8 @@ struct Cfg {
                  "          [--scene NAME] [--device-index N] [--list-devices] [--list-scenes]\n"
                  "          [--assets DIR] [--out FILE.png] [--raw FILE.raw] [--gpus N] [--split sample|tile]\n"
                  "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n"
-                 "          [--adaptive] [--sample-map FILE.raw]\n",
+                 "          [--adaptive] [--sample-map FILE.raw] [--denoise] [--denoise-iters N]\n"
+                 "          [--features FILE.raw]\n",
                  msg);
     std::exit(2);
 }
@@ -102,6 +111,9 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--error-map") c.error_map = val();
         else if (a == "--adaptive") c.adaptive = true;
         else if (a == "--sample-map") c.sample_map = val();
+        else if (a == "--denoise") c.denoise = true;
+        else if (a == "--denoise-iters") c.denoise_iters = std::atoi(val().c_str()), c.have_iters = true;
+        else if (a == "--features") c.features = val();
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
@@ -110,6 +122,9 @@ Cfg parse(int argc, char** argv) {
     if ((c.have_target || !c.error_map.empty()) && c.gpus > 1)
         usage("--noise-target and --error-map need --gpus 1");
     if ((c.adaptive || !c.sample_map.empty()) && c.gpus > 1) usage("--adaptive and --sample-map need --gpus 1");
+    if (c.have_iters && !c.denoise) usage("--denoise-iters needs --denoise");
+    if ((c.denoise || !c.features.empty()) && c.gpus > 1) usage("--denoise and --features need --gpus 1");
+    if (c.have_iters && (c.denoise_iters < 1 || c.denoise_iters > 8)) usage("--denoise-iters must be 1..8");
     if (c.adaptive && !c.have_target) usage("--adaptive needs --noise-target");
     if (!c.sample_map.empty() && !c.adaptive) usage("--sample-map needs --adaptive");
     if (c.adaptive && c.batch < 2) usage("--adaptive needs --batch >= 2");
@@ -125,13 +140,15 @@ Cfg parse(int argc, char** argv) {
 // tiles that took every sample.
 int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, uint64_t stream_seed,
                  std::vector<double>& out, std::vector<double>& se_rgba, uint32_t& done, double& rel,
-                 std::vector<double>& counts_rgba, uint32_t& tiles_at_max, char* err, size_t err_len) {
+                 std::vector<double>& counts_rgba, uint32_t& tiles_at_max, std::vector<double>& normals_rgba, char* err,
+                 size_t err_len) {
     const size_t n = (size_t)c.width * c.height;
     const uint32_t tiles = (uint32_t)((c.width + 7) / 8) * (uint32_t)((c.height + 7) / 8);
     ptmi_scene* sc = nullptr;
     double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *b_sums = nullptr, *b_sq = nullptr, *se = nullptr,
            *stats = nullptr, *tile_err = nullptr;
     uint32_t* lists = nullptr;  // adaptive: two tile lists and the selected count behind them
+    double *feat = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr;  // --denoise / --features
     tiles_at_max = 0;
     int rc = ptmi_scene_create_textured(c.device_index, r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp,
                                         r.camera, tex, &sc, err, err_len);
@@ -147,6 +164,41 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
     double st[4] = {0, 0, 0, 0};
     done = 0;
     rel = 0.0;
+    // The finished frame (image: RGBA, se: the standard-error map, both on the device) to the host,
+    // through the feature pass and the filter when they are asked for.
+    auto finish = [&](const double* image) -> bool {
+        const double* se_final = se;
+        if (c.denoise || !c.features.empty()) {
+            if (hip(hipMalloc((void**)&feat, n * PTMI_FEATURE_DOUBLES * sizeof(double)), "hipMalloc")) return false;
+            if ((rc = ptmi_scene_features(sc, feat, nullptr, err, err_len))) return false;
+        }
+        if (!c.features.empty()) {
+            std::vector<double> fh(n * PTMI_FEATURE_DOUBLES);
+            if (hip(hipMemcpy(fh.data(), feat, fh.size() * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy"))
+                return false;
+            normals_rgba.resize(n * 4);
+            for (size_t i = 0; i < n; i++) {
+                for (int k = 0; k < 3; k++) normals_rgba[4 * i + k] = fh[PTMI_FEATURE_DOUBLES * i + 4 + k] * 0.5 + 0.5;
+                normals_rgba[4 * i + 3] = 1.0;
+            }
+        }
+        if (c.denoise) {
+            const size_t wb = ptmi_denoise_work_bytes((uint32_t)c.width, (uint32_t)c.height);
+            if (hip(hipMalloc((void**)&dn_out, n * 4 * sizeof(double)), "hipMalloc")) return false;
+            if (hip(hipMalloc((void**)&dn_se, n * sizeof(double)), "hipMalloc")) return false;
+            if (hip(hipMalloc((void**)&dn_work, wb), "hipMalloc")) return false;
+            ptmi_denoise_params dp{5, PTMI_DENOISE_DEMODULATE, 4.0, 0.01, 7, 0};
+            if (c.denoise_iters) dp.iterations = (uint32_t)c.denoise_iters;
+            if ((rc = ptmi_denoise(image, se, feat, (uint32_t)c.width, (uint32_t)c.height, &dp, dn_out, dn_se, dn_work,
+                                   wb, nullptr, err, err_len)))
+                return false;
+            image = dn_out;
+            se_final = dn_se;
+        }
+        if (hip(hipMemcpy(out.data(), image, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) return false;
+        if (hip(hipMemcpy(se_host.data(), se_final, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) return false;
+        return true;
+    };
     do {
         if (hip(hipSetDevice(c.device_index), "hipSetDevice")) break;
         if (hip(hipMalloc((void**)&seeds, n * sizeof(double)), "hipMalloc")) break;
@@ -189,7 +241,6 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
             }
             if (rc) break;
             if ((rc = ptmi_finalize_counts(sums, b_sums, (uint32_t)n, nullptr, err, err_len))) break;
-            if (hip(hipMemcpy(out.data(), b_sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
             counts_rgba.resize(n * 4);
             if (hip(hipMemcpy(counts_rgba.data(), sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy"))
                 break;
@@ -197,7 +248,7 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
                 counts_rgba[4 * i + 0] = counts_rgba[4 * i + 1] = counts_rgba[4 * i + 2] = counts_rgba[4 * i + 3];
                 counts_rgba[4 * i + 3] = 1.0;
             }
-            if (hip(hipMemcpy(se_host.data(), se, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+            (void)finish(b_sums);
             break;
         }
         while (done < samples) {
@@ -217,10 +268,9 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
         }
         if (rc) break;
         if ((rc = ptmi_finalize(sums, sums, (uint32_t)n, done, nullptr, err, err_len))) break;
-        if (hip(hipMemcpy(out.data(), sums, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
-        if (hip(hipMemcpy(se_host.data(), se, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+        (void)finish(sums);
     } while (false);
-    for (double* p : {seeds, sums, sq, b_sums, b_sq, se, stats, tile_err})
+    for (double* p : {seeds, sums, sq, b_sums, b_sq, se, stats, tile_err, feat, dn_out, dn_se, dn_work})
         if (p) (void)hipFree(p);
     if (lists) (void)hipFree(lists);
     ptmi_scene_destroy(sc);
@@ -283,7 +333,8 @@ int main(int argc, char** argv) {
     const uint64_t stream =
         c.have_seed ? c.seed : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
     ptmi_multi_timing mt{};
-    const bool noise = c.have_target || !c.error_map.empty();
+    const bool noise = c.have_target || !c.error_map.empty() || c.denoise || !c.features.empty();
+    std::vector<double> normals_rgba;
     std::vector<double> se_rgba;
     uint32_t samples_done = (uint32_t)c.samples;
     double rel_err = 0.0;
@@ -291,7 +342,7 @@ int main(int argc, char** argv) {
     uint32_t tiles_at_max = 0;
     if (noise) {
         rc = render_noise(c, r, textured ? &tex : nullptr, stream, out, se_rgba, samples_done, rel_err, counts_rgba,
-                          tiles_at_max, err, sizeof(err));
+                          tiles_at_max, normals_rgba, err, sizeof(err));
     } else if (c.gpus == 1) {
         rc = ptmi_trace(r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp, c.device_index,
                         (uint32_t)c.samples, r.camera, nullptr, stream, textured ? &tex : nullptr, out.data(), err,
@@ -326,12 +377,17 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s\n", err);
         return 1;
     }
+    if (!c.features.empty() &&
+        (rc = ptmi_host_write_raw(c.features.c_str(), normals_rgba.data(), c.width, c.height, err, sizeof(err)))) {
+        std::fprintf(stderr, "%s\n", err);
+        return 1;
+    }
     if (!c.sample_map.empty() &&
         (rc = ptmi_host_write_raw(c.sample_map.c_str(), counts_rgba.data(), c.width, c.height, err, sizeof(err)))) {
         std::fprintf(stderr, "%s\n", err);
         return 1;
     }
-    if (noise) std::printf("samples_done %u relative_error %.6g\n", samples_done, rel_err);
+    if (c.have_target || !c.error_map.empty()) std::printf("samples_done %u relative_error %.6g\n", samples_done, rel_err);
     double traced = (double)n * samples_done;
     if (c.adaptive) {
         traced = 0.0;

@@ -38,7 +38,10 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_scene_set_timing", "ptmi_scene_kernel_time", "ptmi_trace_multi", "ptmi_scene_create_textured",
            "ptmi_trace_multi_timed", "ptmi_sample_split_point", "ptmi_combine_frames",
            "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate",
-           "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts")
+           "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts", "ptmi_scene_features",
+           "ptmi_denoise", "ptmi_denoise_work_bytes")
+FEATURE_DOUBLES = 12    # PTMI_FEATURE_DOUBLES: doubles per pixel of Scene.features
+DENOISE_DEMODULATE = 1  # PTMI_DENOISE_DEMODULATE
 
 
 class MultiTiming(ctypes.Structure):
@@ -48,6 +51,15 @@ class MultiTiming(ctypes.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DenoiseParams(ctypes.Structure):
+    """ptmi_denoise_params (include/ptmi.h); the constructor's defaults are the library's."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("sigma_l", ctypes.c_double),
+                ("sigma_d", ctypes.c_double), ("normal_power", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def __init__(self, iterations=5, flags=DENOISE_DEMODULATE, sigma_l=4.0, sigma_d=0.01, normal_power=7):
+        super().__init__(iterations, flags, sigma_l, sigma_d, normal_power, 0)
 
 
 class PtmiError(RuntimeError):
@@ -112,6 +124,13 @@ def load_library(path=None):
         lib.ptmi_select_tiles.argtypes = [vp, vp, u32, ctypes.c_double, vp, vp, vp, cp, sz]
         lib.ptmi_finalize_counts.restype = i32
         lib.ptmi_finalize_counts.argtypes = [vp, vp, u32, vp, cp, sz]
+    if hasattr(lib, "ptmi_denoise"):  # (likewise)
+        lib.ptmi_scene_features.restype = i32
+        lib.ptmi_scene_features.argtypes = [vp, vp, vp, cp, sz]
+        lib.ptmi_denoise_work_bytes.restype = sz
+        lib.ptmi_denoise_work_bytes.argtypes = [u32, u32]
+        lib.ptmi_denoise.restype = i32
+        lib.ptmi_denoise.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(DenoiseParams), vp, vp, vp, sz, vp, cp, sz]
     lib.ptmi_finalize.restype = i32
     lib.ptmi_finalize.argtypes = [vp, vp, u32, u32, vp, cp, sz]
     lib.ptmi_fill_seeds.restype = i32
@@ -131,7 +150,7 @@ def load_library(path=None):
     for name, args in (("ptmi_diag_set_knob", [vp, i32, i32]), ("ptmi_diag_force_flags", [i32]),
                        ("ptmi_diag_hemi_mismatch", [vp]), ("ptmi_diag_set_split", [vp, i32]),
                        ("ptmi_diag_split_passes", [vp]), ("ptmi_diag_scene_flags", [vp]),
-                       ("ptmi_diag_tile_ownership", [vp, u32])):
+                       ("ptmi_diag_tile_ownership", [vp, u32]), ("ptmi_diag_denoise_variant", [i32])):
         if hasattr(lib, name):  # (diagnostic libraries of earlier rounds lack some)
             getattr(lib, name).restype = i32
             getattr(lib, name).argtypes = args
@@ -331,6 +350,13 @@ class Scene:
                                      self.width * self.height, samples, ctypes.c_void_p(stream), err, len(err))
         _check(rc, err)
 
+    def features(self, feat_ptr, stream=0):
+        """ptmi_scene_features: the first-hit records of the pinhole rays through the pixel centres,
+        W*H*FEATURE_DOUBLES doubles at feat_ptr (position, t, normal, object id, albedo, 0)."""
+        err = ctypes.create_string_buffer(256)
+        _check(self._lib.ptmi_scene_features(self._h, ctypes.c_void_p(feat_ptr or None), ctypes.c_void_p(stream), err,
+                                             len(err)), err)
+
     def set_rng(self, mode):
         """RNG_NOISE3D (default, the reference's noise3D bit for bit) or RNG_XOSHIRO (the
         opt-in statistical mode: images converge to the same expectation, not equal)."""
@@ -435,3 +461,34 @@ def finalize_counts(sums_ptr, out_ptr, n_pixels, stream=0):
     err = ctypes.create_string_buffer(256)
     _check(load_library().ptmi_finalize_counts(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(out_ptr), int(n_pixels),
                                                ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def denoise_work_bytes(width, height):
+    """ptmi_denoise_work_bytes: the scratch ptmi_denoise needs for a W x H frame."""
+    return load_library().ptmi_denoise_work_bytes(int(width), int(height))
+
+
+def denoise_params(params=None):
+    """A DenoiseParams from None (the defaults), a DenoiseParams or a dict of some of its fields."""
+    if params is None or isinstance(params, DenoiseParams):
+        return params
+    return DenoiseParams(**dict(params))
+
+
+def denoise(rgba_ptr, se_ptr, feat_ptr, w, h, out_ptr, out_se_ptr=0, params=None, stream=0, work=None):
+    """ptmi_denoise: the variance-guided a-trous filter over a W x H frame in device memory -- rgba_ptr
+    (finalize), se_ptr (error_map) and feat_ptr (Scene.features) in, out_ptr (RGBA, must not alias
+    rgba_ptr) and out_se_ptr (optional) out.  params: None, a DenoiseParams or a dict of its fields.
+    The workspace is `work`, a torch tensor of at least denoise_work_bytes(w, h) bytes on the device, or
+    one allocated here on torch's current stream.  The operation order is ptmi/denoise.py
+    atrous_reference."""
+    p = denoise_params(params)
+    if work is None:
+        import torch
+        work = torch.empty(denoise_work_bytes(w, h) // 8, dtype=torch.float64, device="cuda")
+    err = ctypes.create_string_buffer(256)
+    _check(load_library().ptmi_denoise(ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None),
+                                       ctypes.c_void_p(feat_ptr or None), int(w), int(h),
+                                       ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_ptr or None),
+                                       ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(work.data_ptr()),
+                                       work.numel() * work.element_size(), ctypes.c_void_p(stream), err, len(err)), err)
