@@ -316,6 +316,59 @@ int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* fea
                  double* out_se_dev /* may be NULL */, void* work_dev, size_t work_bytes, void* hip_stream,
                  char* err, size_t err_len);
 
+/*
+ * Temporal accumulation (the temporal part of SVGF): this frame blended into the history of the
+ * surface points it shows, found in the previous frame by reprojecting each pixel's first hit.
+ *   rgba_dev, se_dev, feat_dev   this frame, its standard-error map and its first-hit records
+ *                                (ptmi_finalize, ptmi_error_map, ptmi_scene_features)
+ *   prev_hist_dev, prev_feat_dev the previous frame's history (an earlier call's out_hist_dev) and
+ *                                records; prev_hist_dev == NULL: the first frame, every pixel resets
+ *                                (prev_feat_dev and prev_camera may then be NULL too)
+ *   prev_camera                  HOST pointer to the previous frame's 256-byte CLCamera; its `inverse`
+ *                                is inverted on the host (FP64 cofactors) into the world-to-camera matrix
+ *   out_hist_dev                 W*H*PTMI_HISTORY_DOUBLES doubles per pixel: [0..2] the accumulated colour,
+ *                                [3] its variance (se^2), [4] the history length N, [5..7] 0
+ *   out_rgba_dev (may be NULL)   (accumulated colour, 1.0): with out_se_dev what ptmi_denoise takes
+ *   out_se_dev   (may be NULL)   sqrt(variance)
+ * A pixel RESETS to (rgb, se^2, N = 1) when there is no history, when it is a miss, when its point lies
+ * behind the previous camera or its accepted bilinear weight W is below min_weight (or 0); a pixel whose
+ * colour or se is not finite resets with N = 0 and is read by no later frame.  Otherwise, over the four
+ * bilinear taps around the point's place in the previous image that are inside it, hold history
+ * (N > 0, finite), show the same object, and pass the normal and plane-distance tests below:
+ *   W = sum w;  h_c = rgb + (sum w (c_q - rgb)) / W;  h_var = (sum w^2 var_q) / W^2;  h_N = (sum w N_q) / W;
+ *   N' = min(h_N + 1, max_history),  a = 1 / N';  colour' = h_c + a (rgb - h_c);
+ *   var' = a^2 se^2 + (1 - a)^2 h_var.
+ * h_c is the taps' weighted mean sum w c_q / W, computed around this frame's colour: in that order a
+ * sequence of equal colours stays equal bit for bit whatever the rounding of the projected place, which
+ * the plain quotient does not give.  The exact operation order is ptmi/temporal.py reproject_reference.  The variance formula takes the
+ * frames for INDEPENDENT estimates: render them with different seeds.  Two frames with equal seeds and
+ * an unchanged camera are the same estimate, and averaging them halves nothing.
+ * The guides are the pinhole ray through the pixel centre: the first hit on glass or a mirror
+ * reprojects the glass, not what shows through it, and view-dependent shading lags by the history
+ * length; the scene is static, only the camera moves; at 1 spp se is +inf and every pixel resets.
+ * Allocates nothing; asynchronous on the stream.  No output may overlap an input or another output, in
+ * whole or in part (callers ping-pong two history buffers; there is no in-place form: out_rgba_dev is
+ * not rgba_dev, out_se_dev is not se_dev); the ranges are checked.  Every buffer but se_dev and
+ * out_se_dev must be 16-byte aligned.
+ * PTMI_ERR_ARG (no launch, no device call) for a NULL required pointer, zero width or height,
+ * max_history outside 1..65536, non-zero flags, a negative or non-finite threshold, overlapping or
+ * misaligned buffers, and a prev_camera that is singular, not finite or of another width or height.
+ */
+#define PTMI_HISTORY_DOUBLES 8
+typedef struct ptmi_reproject_params {
+    uint32_t max_history; /* default 32; 1..65536 */
+    uint32_t flags;       /* 0 */
+    double normal_cos;    /* default 0.9 : a tap is rejected when n_p . n_q <  normal_cos */
+    double plane_dist;    /* default 0.02: ... when |n_p . (x_q - x_p)| > plane_dist * t_p */
+    double min_weight;    /* default 0.05: history is dropped when the accepted bilinear weight is below it */
+} ptmi_reproject_params;
+
+int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                   const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
+                   uint32_t width, uint32_t height, const ptmi_reproject_params* params /* NULL = defaults */,
+                   double* out_hist_dev, double* out_rgba_dev /* may be NULL */, double* out_se_dev /* may be NULL */,
+                   void* hip_stream, char* err, size_t err_len);
+
 /* dst_dev[k] += src_dev[k] over n doubles, on the caller's stream: batches of sums
  * (A included, so the sample counts add) and of second moments. */
 int ptmi_accumulate(double* dst_dev, const double* src_dev, size_t n, void* hip_stream, char* err,
@@ -339,6 +392,22 @@ int ptmi_fill_seeds(double* seeds_dev, uint32_t n, uint64_t seed_stream, void* h
  * untextured scenes only (else PTMI_ERR_UNSUPPORTED). */
 enum { PTMI_RNG_NOISE3D = 0, PTMI_RNG_XOSHIRO = 1 };
 int ptmi_scene_set_rng(ptmi_scene* s, int mode, char* err, size_t err_len);
+
+/* A new camera (256-byte CLCamera) on a resident scene.  Afterwards the scene is what
+ * ptmi_scene_create gives for the same objects, triangles, groups and textures with this camera:
+ * every later render, moment render, tile render and feature pass is bit-identical to the fresh
+ * scene's.  Nothing but the camera is converted or uploaded: the record, its origin (the create
+ * call's own arithmetic), the kernel instantiation it selects (depth of field, affine or not -- a
+ * camera can move a scene between instantiations), the camera terms behind the record, and, for mesh
+ * scenes, the tile classes and the dispatch order.  Width and height must be the scene's (buffers and
+ * work plans depend on them): else, or for a NULL scene or record, PTMI_ERR_ARG.  In the statistical
+ * RNG mode a camera that makes the scene non-affine is PTMI_ERR_UNSUPPORTED.  Everything is checked
+ * before anything changes: after PTMI_ERR_ARG or PTMI_ERR_UNSUPPORTED the scene renders exactly as
+ * before.  PTMI_ERR_HIP (a runtime call failed during the update) may leave the record, the flags and
+ * the tile classes partly updated: set the camera again, or destroy the scene.
+ * HOST-BLOCKING: the call waits for all earlier work of the device (renders in flight read the camera
+ * record in device memory) and returns after the upload and the terms pass have completed. */
+int ptmi_scene_set_camera(ptmi_scene* s, const void* camera, char* err, size_t err_len);
 
 /* Kernel timing: with timing enabled, every trace_kernel launch of the scene is
  * bracketed by HIP events recorded on the launch stream; ptmi_scene_kernel_time

@@ -42,6 +42,10 @@ int ptmi_diag_tile_cost(const void* objects, uint32_t n_obj, const void* triangl
                         const void* groups, uint32_t n_grp, const void* camera, uint8_t* out, uint32_t n_out,
                         char* err, size_t err_len);
 
+/* ptmi_diag_tile_cost for a resident scene, through the scene's own cache of tile classes: what its
+ * next ordered render sorts by (after ptmi_scene_set_camera: the new view's).  Host only. */
+int ptmi_diag_scene_tile_cost(ptmi_scene* s, uint8_t* out, uint32_t n_out, char* err, size_t err_len);
+
 /* Mesh-scene execution form (study build; the product has only the one-kernel form and
  * returns PTMI_ERR_UNSUPPORTED for enable != 0): enable != 0 renders affine mesh scenes in
  * the split form (trace_split_kernel + walk_split_kernel, pass by pass), 0 (the default)

@@ -55,6 +55,9 @@ hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st);
 hipError_t launch_denoise(const double* rgba, const double* se, const double* feat, uint32_t W, uint32_t H,
                           uint32_t iterations, bool demod, double sigma_l, double sigma_d, uint32_t npow, double* out,
                           double* out_se, double* work, int variant, hipStream_t st);
+hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
+                            const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
+                            double* out_se, hipStream_t st);
 const void* trace_kernel_symbol(int flags);
 bool tile_list_supported(int flags);
 int trace_kernel_flags(int flags);
@@ -84,6 +87,17 @@ struct TileCostInput {
         std::vector<std::array<double, 6>> hulls;  // (mn xyz, mx xyz) per root
     };
     std::vector<Obj> objs;
+};
+
+// The kernel flags of a scene (ptmi_kernels.hip F_*) in two parts: what the objects, the triangles, the
+// traversal index and the force hook decide (SceneFlagBasis, fixed when the scene is created), and what the
+// camera adds (scene_flags), so that a camera change re-derives the instantiation from the same code.
+struct SceneFlagBasis {
+    int obj_bits = 0;       // F_GROUPS | F_CYLCUBE | F_MATERIALS
+    bool affine = true;     // every object and triangle normal passes the affine test below
+    bool textured = false;  // the one textured instantiation
+    int forced = -1;        // ptmi_diag_force_flags at creation (-1: none)
+    int wide = 0;           // F_WIDE
 };
 
 struct ptmi_scene {
@@ -123,6 +137,7 @@ struct ptmi_scene {
     bool order_tlist = false;  // the dispatch order was built for a list launch
     uint32_t width = 0, height = 0;
     int flags = 0;  // scene features -> kernel instantiation (ptmi_kernels.hip F_*)
+    SceneFlagBasis basis;  // what `flags` takes from everything but the camera (ptmi_scene_set_camera)
     int hemi_mismatch = 0;  // hemisphere-table records where affine and generic sequences differ (upload_scene)
     int rng = PTMI_RNG_NOISE3D;  // ptmi_scene_set_rng: PTMI_RNG_XOSHIRO launches the F_XRNG instantiations
     bool timing = false;
@@ -215,19 +230,9 @@ bool is_diag3(const double* m) {  // rows 0-2 diagonal (row 3 unused)
     return true;
 }
 
-int convert_scene(const uint8_t* objects, uint32_t n_obj, const uint8_t* tris, uint32_t n_tri, const uint8_t* groups,
-                  uint32_t n_grp, const uint8_t* camera, std::vector<DevObject>& objs, std::vector<int32_t>& roots,
-                  std::vector<DevNode>& nodes, RootIndex& index, std::vector<RootRec>& root_rec,
-                  std::vector<DevTriShade>& st, DevCamera& cam, int32_t run_end[5], char* err, size_t err_len) {
-    if (!objects || n_obj == 0 || n_obj > PTMI_MAX_OBJECTS) {
-        set_err(err, err_len, "need 1..%d objects (tracer.cl:846 __local object objects[16]), got %u",
-                PTMI_MAX_OBJECTS, n_obj);
-        return PTMI_ERR_ARG;
-    }
-    if (!camera || (n_tri && !tris) || (n_grp && !groups)) {
-        set_err(err, err_len, "NULL record pointer");
-        return PTMI_ERR_ARG;
-    }
+// The 256-byte CLCamera record -> DevCamera, origin included: the one conversion behind
+// ptmi_scene_create and ptmi_scene_set_camera, so both give the kernels the same bits.
+int convert_camera(const uint8_t* camera, DevCamera& cam, char* err, size_t err_len) {
     cam.width = rd<int32_t>(camera + 0);
     cam.height = rd<int32_t>(camera + 4);
     cam.pixel_size = rd<double>(camera + 16);
@@ -243,6 +248,23 @@ int convert_scene(const uint8_t* objects, uint32_t n_obj, const uint8_t* tris, u
         set_err(err, err_len, "bad camera size %dx%d", cam.width, cam.height);
         return PTMI_ERR_ARG;
     }
+    return PTMI_OK;
+}
+
+int convert_scene(const uint8_t* objects, uint32_t n_obj, const uint8_t* tris, uint32_t n_tri, const uint8_t* groups,
+                  uint32_t n_grp, const uint8_t* camera, std::vector<DevObject>& objs, std::vector<int32_t>& roots,
+                  std::vector<DevNode>& nodes, RootIndex& index, std::vector<RootRec>& root_rec,
+                  std::vector<DevTriShade>& st, DevCamera& cam, int32_t run_end[5], char* err, size_t err_len) {
+    if (!objects || n_obj == 0 || n_obj > PTMI_MAX_OBJECTS) {
+        set_err(err, err_len, "need 1..%d objects (tracer.cl:846 __local object objects[16]), got %u",
+                PTMI_MAX_OBJECTS, n_obj);
+        return PTMI_ERR_ARG;
+    }
+    if (!camera || (n_tri && !tris) || (n_grp && !groups)) {
+        set_err(err, err_len, "NULL record pointer");
+        return PTMI_ERR_ARG;
+    }
+    if (const int rc = convert_camera(camera, cam, err, err_len)) return rc;
     std::vector<DevObject> all(n_obj);
     for (uint32_t i = 0; i < n_obj; i++) {
         const uint8_t* b = objects + (size_t)PTMI_OBJECT_BYTES * i;
@@ -355,6 +377,40 @@ int upload(const std::vector<T>& v, void** dst, char* err, size_t err_len) {
 }
 
 
+// The affine instantiations also use the compiler's divide / sqrt cores for sphere
+// roots (ptmi_kernels.hip div_core), which needs 2a = 2|M d|^2
+// far above the denormal range for every unit-scale ray direction d: each sphere's
+// inverse has linear-part entries <= 2^64 and |det| >= 2^-64, so its smallest singular
+// value is >= 2^-196.  Scenes outside that take the generic instantiation.
+// The same bound on the camera inverse keeps |pixel - origin| >= 2^-196 for its
+// normalize's core, and on sphere inverses (through their transposes) keeps sphere
+// normals >= 2^-196 long.
+bool tame(const double* m) {
+    double mx = 0.0;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) mx = std::max(mx, std::fabs(m[4 * r + c]));
+    const double det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) +
+                       m[2] * (m[4] * m[9] - m[5] * m[8]);
+    return mx <= 0x1p64 && std::fabs(det) >= 0x1p-64;
+}
+
+// Affine camera (ptmi_kernels.hip dotv): the inverse ends in (+-0, +-0, +-0, 1) and is tame.
+bool camera_affine(const DevCamera& cam) {
+    return cam.inv[12] == 0.0 && cam.inv[13] == 0.0 && cam.inv[14] == 0.0 && cam.inv[15] == 1.0 && tame(cam.inv);
+}
+
+int scene_flags(const SceneFlagBasis& fb, const DevCamera& cam) {
+    int flags = fb.obj_bits;
+    if (cam.aperture != 0) flags |= 8;                                  // F_DOF
+    // Affine scene: every inverse ends in (+-0, +-0, +-0, 1), inverse transposes have +-0 in
+    // column 3 of rows 0-2, triangle normals have a finite w.  Otherwise F_PROJ: the generic
+    // instantiation with the w lanes.
+    if (!(fb.affine && camera_affine(cam))) flags |= 16;                // F_PROJ
+    if (fb.textured) flags = 63;
+    if (fb.forced >= 0) flags = fb.forced & 63;
+    return flags | fb.wide;  // (never a 16-bit stack for 31-bit codes: F_PROJ and F_TEX kernels have 32-bit ones)
+}
+
 // A scene converted on the host once (records validated and split into the device
 // layouts, traversal indices built, kernel flags chosen), uploadable to any device.
 struct HostScene {
@@ -369,6 +425,7 @@ struct HostScene {
     DevCamera cam{};
     int32_t run_end[5] = {};
     int flags = 0;
+    SceneFlagBasis basis;
     int32_t leaf_bit = kLeafNarrow;  // Node4 child code format (finalize_index_codes)
     uint32_t n_list = 0, n_grp = 0, n_tri = 0;
     int32_t n_planes_y = 0;
@@ -382,54 +439,32 @@ int prepare_scene(const void* objects, uint32_t n_obj, const void* triangles, ui
                            hs.cam, hs.run_end, err, err_len);
     if (rc) return rc;
     hs.leaf_bit = finalize_index_codes(hs.index, hs.root_rec);
-    const DevCamera& cam = hs.cam;
-    int flags = 0;
+    // What the flags take from the objects, the triangles and the force hook (SceneFlagBasis); the camera's
+    // part is scene_flags', which ptmi_scene_set_camera runs again.
+    SceneFlagBasis& fb = hs.basis;
+    fb = SceneFlagBasis{};
     for (const DevObject& o : hs.objs) {
-        if (o.type == 4) flags |= 1;                                    // F_GROUPS
-        if (o.type == 2 || o.type == 3) flags |= 2;                     // F_CYLCUBE
-        if (o.reflectivity != 0.0 || o.refractive_index != 1.0) flags |= 4;  // F_MATERIALS
+        if (o.type == 4) fb.obj_bits |= 1;                                    // F_GROUPS
+        if (o.type == 2 || o.type == 3) fb.obj_bits |= 2;                     // F_CYLCUBE
+        if (o.reflectivity != 0.0 || o.refractive_index != 1.0) fb.obj_bits |= 4;  // F_MATERIALS
     }
-    if (cam.aperture != 0) flags |= 8;                                  // F_DOF
-    // Affine scene (ptmi_kernels.hip dotv): every inverse ends in (+-0, +-0, +-0, 1),
-    // inverse transposes have +-0 in column 3 of rows 0-2, triangle normals have a
-    // finite w.  Otherwise F_PROJ: the generic instantiation with the w lanes.
-    bool affine = cam.inv[12] == 0.0 && cam.inv[13] == 0.0 && cam.inv[14] == 0.0 && cam.inv[15] == 1.0;
     for (const DevObject& o : hs.objs)
-        affine = affine && o.inv[12] == 0.0 && o.inv[13] == 0.0 && o.inv[14] == 0.0 && o.inv[15] == 1.0 &&
-                 o.inv_t[3] == 0.0 && o.inv_t[7] == 0.0 && o.inv_t[11] == 0.0;
+        fb.affine = fb.affine && o.inv[12] == 0.0 && o.inv[13] == 0.0 && o.inv[14] == 0.0 && o.inv[15] == 1.0 &&
+                    o.inv_t[3] == 0.0 && o.inv_t[7] == 0.0 && o.inv_t[11] == 0.0;
     for (const DevTriShade& t : hs.st)
-        affine = affine && std::isfinite(t.n1[3]) && std::isfinite(t.n2[3]) && std::isfinite(t.n3[3]);
-    // The affine instantiations also use the compiler's divide / sqrt cores for sphere
-    // roots (ptmi_kernels.hip div_core), which needs 2a = 2|M d|^2
-    // far above the denormal range for every unit-scale ray direction d: each sphere's
-    // inverse has linear-part entries <= 2^64 and |det| >= 2^-64, so its smallest singular
-    // value is >= 2^-196.  Scenes outside that take the generic instantiation.
-    // The same bound on the camera inverse keeps |pixel - origin| >= 2^-196 for its
-    // normalize's core, and on sphere inverses (through their transposes) keeps sphere
-    // normals >= 2^-196 long.
-    auto tame = [](const double* m) {
-        double mx = 0.0;
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) mx = std::max(mx, std::fabs(m[4 * r + c]));
-        const double det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) +
-                           m[2] * (m[4] * m[9] - m[5] * m[8]);
-        return mx <= 0x1p64 && std::fabs(det) >= 0x1p-64;
-    };
-    affine = affine && tame(cam.inv);
+        fb.affine = fb.affine && std::isfinite(t.n1[3]) && std::isfinite(t.n2[3]) && std::isfinite(t.n3[3]);
     for (const DevObject& o : hs.objs)
-        if (o.type == 1) affine = affine && tame(o.inv);
-    if (!affine) flags |= 16;                                           // F_PROJ
+        if (o.type == 1) fb.affine = fb.affine && tame(o.inv);
     // Child codes past 16 bits (>= 2^15 Node4s or triangles): a traversal stack of 32-bit
     // entries -- the affine F_WIDE instantiation (ptmi_kernels.hip trace_groups), or the
     // generic one for non-affine scenes (round 5 sent every such scene to the generic one).
-    const int wide = hs.leaf_bit != kLeafNarrow ? 256 : 0;              // F_WIDE
+    fb.wide = hs.leaf_bit != kLeafNarrow ? 256 : 0;                           // F_WIDE
     // Textured plane/sphere/cube colours or plane normal maps: the one textured
     // instantiation (generic arithmetic + software sampler, tracer.cl:907-914, 1077-1092).
     for (const DevObject& o : hs.objs)
-        if ((o.tex && (o.type == 0 || o.type == 1 || o.type == 3)) || (o.tex_nm && o.type == 0)) flags = 63;
-    const int forced = g_force_flags.load();  // ptmi_diag_force_flags (tests): one load
-    if (forced >= 0) flags = forced & 63;
-    flags |= wide;  // (never a 16-bit stack for 31-bit codes: F_PROJ and F_TEX kernels have 32-bit ones)
+        if ((o.tex && (o.type == 0 || o.type == 1 || o.type == 3)) || (o.tex_nm && o.type == 0)) fb.textured = true;
+    fb.forced = g_force_flags.load();  // ptmi_diag_force_flags (tests): one load
+    const int flags = scene_flags(fb, hs.cam);
     if (textures) {
         for (int k = 0; k < 3; k++) {
             const uint64_t texels = (uint64_t)textures->width[k] * textures->height[k] * textures->count[k];
@@ -600,6 +635,7 @@ int upload_scene(const HostScene& hs, int device_index, const ptmi_textures* tex
     HIP_TRY(hipSetDevice(device_index));
     ptmi_scene* s = new ptmi_scene();
     s->flags = hs.flags;
+    s->basis = hs.basis;
     s->device = device_index;
     s->width = (uint32_t)hs.cam.width;
     s->height = (uint32_t)hs.cam.height;
@@ -1396,6 +1432,140 @@ int ptmi_scene_set_rng(ptmi_scene* s, int mode, char* err, size_t err_len) {
     return PTMI_OK;
 }
 
+int ptmi_scene_set_camera(ptmi_scene* s, const void* camera, char* err, size_t err_len) {
+    if (!s || !camera) {
+        set_err(err, err_len, "ptmi_scene_set_camera: scene or camera == NULL");
+        return PTMI_ERR_ARG;
+    }
+    // Everything is checked before anything changes: after an error the scene renders as before.
+    DevCamera cam{};
+    if (const int rc = convert_camera((const uint8_t*)camera, cam, err, err_len)) return rc;
+    if ((uint32_t)cam.width != s->width || (uint32_t)cam.height != s->height) {
+        set_err(err, err_len, "ptmi_scene_set_camera: a %dx%d camera on a %ux%u scene (buffers and work plans keep their size)",
+                cam.width, cam.height, s->width, s->height);
+        return PTMI_ERR_ARG;
+    }
+    const int flags = scene_flags(s->basis, cam);
+    if (s->rng == PTMI_RNG_XOSHIRO && (flags & (16 | 32))) {  // F_PROJ | F_TEX, as ptmi_scene_set_rng
+        set_err(err, err_len, "the statistical RNG mode exists for affine scenes only (this camera is not affine)");
+        return PTMI_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // renders in flight read the record and its terms in device memory
+    HIP_TRY(hipMemcpy(s->buffers[14], &cam, sizeof(DevCamera), hipMemcpyHostToDevice));
+    s->dev.cam = cam;
+    s->flags = flags;
+    // the camera terms go with every upload of the camera record (upload_scene)
+    HIP_TRY(launch_camera_terms(s->dev, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(resident_waves(s));  // the instantiation may have changed (F_DOF, F_PROJ): the work plan's size
+    if (s->flags & 1) {  // mesh scenes: the tile classes and the dispatch order built from them
+        s->tc_in.cam = cam;
+        s->tile_cost.clear();
+        s->order_n = 0;
+    }
+    return PTMI_OK;
+}
+
+// The world-to-camera matrix of a camera record: the FP64 cofactor inverse of its `inverse`
+// (ptmi/temporal.py cofactor_inverse states the same operations).  false: singular or not finite.
+static bool cofactor_inverse(const double* m, double* out) {
+    auto det3 = [&](const int* r, const int* c) {
+        auto a = [&](int i, int j) { return m[4 * r[i] + c[j]]; };
+        return (a(0, 0) * (a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1)) - a(0, 1) * (a(1, 0) * a(2, 2) - a(1, 2) * a(2, 0))) +
+               a(0, 2) * (a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0));
+    };
+    double adj[16];
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {  // adj[i][j] = (-1)^(i+j) * minor of m without row j and column i
+            int r[3], c[3];
+            for (int k = 0, a = 0, b = 0; k < 4; k++) {
+                if (k != j) r[a++] = k;
+                if (k != i) c[b++] = k;
+            }
+            const double d = det3(r, c);
+            adj[4 * i + j] = ((i + j) & 1) ? -d : d;
+        }
+    const double det = ((m[0] * adj[0] + m[1] * adj[4]) + m[2] * adj[8]) + m[3] * adj[12];
+    if (!std::isfinite(det) || det == 0.0) return false;
+    for (int k = 0; k < 16; k++) {
+        out[k] = adj[k] / det;
+        if (!std::isfinite(out[k])) return false;
+    }
+    return true;
+}
+
+int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* prev_hist_dev,
+                   const double* prev_feat_dev, const void* prev_camera, uint32_t width, uint32_t height,
+                   const ptmi_reproject_params* params, double* out_hist_dev, double* out_rgba_dev, double* out_se_dev,
+                   void* hip_stream, char* err, size_t err_len) {
+    ptmi_reproject_params p{32, 0, 0.9, 0.02, 0.05};
+    if (params) p = *params;
+    if (!rgba_dev || !se_dev || !feat_dev || !out_hist_dev || (prev_hist_dev && (!prev_feat_dev || !prev_camera)) ||
+        width == 0 || height == 0 || width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
+        set_err(err, err_len, "bad reproject arguments (%u x %u)", width, height);
+        return PTMI_ERR_ARG;
+    }
+    auto good = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (p.max_history < 1 || p.max_history > 65536 || p.flags != 0 || !good(p.normal_cos) || !good(p.plane_dist) ||
+        !good(p.min_weight)) {
+        set_err(err, err_len, "bad reproject parameters (max_history %u flags %u normal_cos %g plane_dist %g min_weight %g)",
+                p.max_history, p.flags, p.normal_cos, p.plane_dist, p.min_weight);
+        return PTMI_ERR_ARG;
+    }
+    // No output may overlap an input or another output (the kernel's pointers are __restrict__).
+    const size_t npix = (size_t)width * height;
+    struct Range {
+        const double* p;
+        size_t doubles;
+    };
+    const Range ins[5] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
+                          {prev_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {prev_feat_dev, npix * PTMI_FEATURE_DOUBLES}};
+    const Range outs[3] = {{out_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {out_rgba_dev, npix * 4}, {out_se_dev, npix}};
+    auto overlap = [](const Range& a, const Range& b) {
+        if (!a.p || !b.p) return false;
+        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+        return a0 < b0 + b.doubles * sizeof(double) && b0 < a0 + a.doubles * sizeof(double);
+    };
+    bool aliased = false;
+    for (int o = 0; o < 3; o++) {
+        for (int i = 0; i < 5; i++) aliased = aliased || overlap(outs[o], ins[i]);
+        for (int q = o + 1; q < 3; q++) aliased = aliased || overlap(outs[o], outs[q]);
+    }
+    if (aliased ||
+        (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)prev_hist_dev | (uintptr_t)prev_feat_dev |
+          (uintptr_t)out_hist_dev | (uintptr_t)out_rgba_dev) & 15u)) {
+        set_err(err, err_len, "reproject buffers overlap or are not 16-byte aligned");
+        return PTMI_ERR_ARG;
+    }
+    ReprojectArgs a{};
+    a.W = (int32_t)width;
+    a.H = (int32_t)height;
+    a.max_history = (double)p.max_history;
+    a.normal_cos = p.normal_cos;
+    a.plane_dist = p.plane_dist;
+    a.min_weight = p.min_weight;
+    if (prev_camera) {
+        DevCamera cam{};
+        if (const int rc = convert_camera((const uint8_t*)prev_camera, cam, err, err_len)) return rc;
+        double T[16];
+        if ((uint32_t)cam.width != width || (uint32_t)cam.height != height || !cofactor_inverse(cam.inv, T) ||
+            !(std::isfinite(cam.pixel_size) && cam.pixel_size > 0.0) || !std::isfinite(cam.half_width) ||
+            !std::isfinite(cam.half_height)) {
+            set_err(err, err_len, "reproject: bad previous camera (%dx%d for a %ux%u frame, singular or non-finite)",
+                    cam.width, cam.height, width, height);
+            return PTMI_ERR_ARG;
+        }
+        std::memcpy(a.T, T, sizeof(a.T));  // rows 0-2: the point's camera-space x, y, z
+        a.half_width = cam.half_width;
+        a.half_height = cam.half_height;
+        a.pixel_size = cam.pixel_size;
+    }
+    HIP_TRY(launch_reproject(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev, out_rgba_dev,
+                             out_se_dev, (hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
 int ptmi_scene_set_timing(ptmi_scene* s, int enable) {
     if (!s) return PTMI_ERR_ARG;
     s->timing = enable != 0;
@@ -1797,6 +1967,25 @@ extern "C" int ptmi_diag_tile_cost(const void* objects, uint32_t n_obj, const vo
         std::vector<uint8_t> c;
         mesh_tile_cost(tile_cost_input(hs), c, tiles, [](uint32_t k) { return k; });
         std::memcpy(out, c.data(), tiles);
+    } else {
+        std::memset(out, 0, tiles);
+    }
+    return PTMI_OK;
+}
+
+extern "C" int ptmi_diag_scene_tile_cost(ptmi_scene* s, uint8_t* out, uint32_t n_out, char* err, size_t err_len) {
+    if (!s || !out) {
+        set_err(err, err_len, "scene or out == NULL");
+        return PTMI_ERR_ARG;
+    }
+    const uint32_t tiles = ((s->width + 7) / 8) * ((s->height + 7) / 8);
+    if (n_out < tiles) {
+        set_err(err, err_len, "out holds %u tiles, the frame has %u", n_out, tiles);
+        return PTMI_ERR_ARG;
+    }
+    if (s->flags & 1) {  // through the scene's own cache: the classes its next ordered render sorts by
+        mesh_tile_cost(s->tc_in, s->tile_cost, tiles, [](uint32_t k) { return k; });
+        std::memcpy(out, s->tile_cost.data(), tiles);
     } else {
         std::memset(out, 0, tiles);
     }

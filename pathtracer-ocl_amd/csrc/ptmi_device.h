@@ -192,6 +192,15 @@ inline size_t cam_record_bytes(int32_t n_planes, int32_t n_spheres_st) {
 }
 static_assert(sizeof(DevCamera) % sizeof(double) == 0, "the terms follow the record as doubles");
 
+// ptmi_reproject's wave-uniform arguments, passed by value (scalar registers): rows 0-2 of the previous
+// camera's world-to-camera matrix, its pixel mapping, and the thresholds.
+struct ReprojectArgs {
+    int32_t W, H;
+    double T[12];
+    double half_width, half_height, pixel_size;
+    double max_history, normal_cos, plane_dist, min_weight;
+};
+
 // One BVH walk of a ray (walk_kernel / walk_pool_kernel): the world-space ray and the
 // best primitive hit so far (t, pk as Hit::pk), one 64-B line; and its result, the
 // closest hit over the primitives and every group object (tri / ti -1 when no triangle

@@ -3340,6 +3340,110 @@ hipError_t launch_denoise(const double* rgba, const double* se, const double* fe
     return hipGetLastError();
 }
 
+// ---- Temporal accumulation (ptmi_reproject) ----------------------------------------------------
+// One thread per pixel on the denoise passes' 16 x 16 blocks: a wave covers 4 rows of 16 pixels, so
+// its own loads and stores are 512-B (frame) and 1-KB (history) runs of 16-B accesses, and its taps
+// into the previous frame -- neighbouring pixels project to neighbouring places -- stay within a few
+// rows.  Per pixel 136 B of its own frame, up to four taps of 48 B history and 64 B of a record, 64 B
+// (+ 40 B) out: bandwidth-bound, no LDS.  Every FP64 operation is separately rounded and in the
+// order ptmi/temporal.py reproject_reference states; the matrix, the camera scalars and the
+// thresholds are by-value arguments (scalar registers).
+__global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __restrict__ rgba,
+                                                                const double* __restrict__ se,
+                                                                const double* __restrict__ feat,
+                                                                const double* __restrict__ prev_hist,
+                                                                const double* __restrict__ prev_feat,
+                                                                ReprojectArgs a, double* __restrict__ out_hist,
+                                                                double* __restrict__ out_rgba,
+                                                                double* __restrict__ out_se) {
+    const int W = a.W, H = a.H;
+    const int x = (int)blockIdx.x * kDnX + (int)threadIdx.x % kDnX, y = (int)blockIdx.y * kDnY + (int)threadIdx.x / kDnX;
+    if (x >= W || y >= H) return;
+    const size_t i = (size_t)y * W + x;
+    const double2* p = reinterpret_cast<const double2*>(rgba + 4 * i);
+    const double2* f = reinterpret_cast<const double2*>(feat + 12 * i);
+    const double2 p0 = p[0], p1 = p[1], f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
+    const double s = se[i];
+    const double c0 = p0.x, c1 = p0.y, c2 = p1.x;
+    const double px = f0.x, py = f0.y, pz = f1.x, pt = f1.y, n0 = f2.x, n1 = f2.y, n2 = f3.x, id = f3.y;
+    const double v = s * s;
+    const bool fin = dn_finite(c0, c1, c2, s);
+    // the reset: this frame alone (a pixel that is not finite is no history for the next frame)
+    double o0 = c0, o1 = c1, o2 = c2, ov = v, on = fin ? 1.0 : 0.0;
+    if (prev_hist != nullptr && fin && !(id < 0.0)) {
+        const double* T = a.T;
+        const double qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
+        const double qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
+        const double z = -(((T[8] * px + T[9] * py) + T[10] * pz) + T[11]);
+        if (z > 0.0) {
+            const double fu = (a.half_width - qx / z) / a.pixel_size - 0.5;
+            const double fv = (a.half_height - qy / z) / a.pixel_size - 0.5;
+            const double fx0 = floor(fu), fy0 = floor(fv);
+            const double wx = fu - fx0, wy = fv - fy0;
+            const double bound = a.plane_dist * pt;
+            double sw = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0, sv = 0.0, sn = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {  // taps (0,0), (1,0), (0,1), (1,1)
+                const int ti = k & 1, tj = k >> 1;
+                const double tx = fx0 + (double)ti, ty = fy0 + (double)tj;
+                // in double: a NaN or a huge coordinate fails the test before any conversion
+                if (!(tx >= 0.0 && tx < (double)W && ty >= 0.0 && ty < (double)H)) continue;
+                const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
+                const double2* hq = reinterpret_cast<const double2*>(prev_hist + 8 * q);
+                const double2 h0 = hq[0], h1 = hq[1], h2 = hq[2];
+                if (!(h2.x > 0.0) || !dn_finite(h0.x, h0.y, h1.x, h1.y)) continue;
+                const double2* fq = reinterpret_cast<const double2*>(prev_feat + 12 * q);
+                const double2 g0 = fq[0], g1 = fq[1], g2 = fq[2], g3 = fq[3];
+                if (g3.y != id) continue;
+                const double dn = (n0 * g2.x + n1 * g2.y) + n2 * g3.x;
+                if (!(dn >= a.normal_cos)) continue;
+                const double dd = (n0 * (g0.x - px) + n1 * (g0.y - py)) + n2 * (g1.x - pz);
+                if (!(fabs(dd) <= bound)) continue;
+                const double w = (ti ? wx : 1.0 - wx) * (tj ? wy : 1.0 - wy);
+                sw = sw + w;
+                r0 = r0 + w * (h0.x - c0);
+                r1 = r1 + w * (h0.y - c1);
+                r2 = r2 + w * (h1.x - c2);
+                sv = sv + (w * w) * h1.y;
+                sn = sn + w * h2.x;
+            }
+            if (sw >= a.min_weight && sw > 0.0) {
+                // the history's weighted mean written around this frame's colour, and the blend around
+                // the history: a constant sequence stays constant bit for bit
+                const double h0 = c0 + r0 / sw, h1 = c1 + r1 / sw, h2 = c2 + r2 / sw;
+                const double hv = sv / (sw * sw), hn = sn / sw;
+                const double np1 = hn + 1.0;
+                on = np1 < a.max_history ? np1 : a.max_history;
+                const double al = 1.0 / on, be = 1.0 - al;
+                o0 = h0 + al * (c0 - h0);
+                o1 = h1 + al * (c1 - h1);
+                o2 = h2 + al * (c2 - h2);
+                ov = (al * al) * v + (be * be) * hv;
+            }
+        }
+    }
+    double2* oh = reinterpret_cast<double2*>(out_hist + 8 * i);
+    oh[0] = make_double2(o0, o1);
+    oh[1] = make_double2(o2, ov);
+    oh[2] = make_double2(on, 0.0);
+    oh[3] = make_double2(0.0, 0.0);
+    if (out_rgba) {
+        double2* o = reinterpret_cast<double2*>(out_rgba + 4 * i);
+        o[0] = make_double2(o0, o1);
+        o[1] = make_double2(o2, 1.0);
+    }
+    if (out_se) out_se[i] = sqrt(ov);
+}
+
+hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
+                            const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
+                            double* out_se, hipStream_t st) {
+    const dim3 grid(((uint32_t)a.W + kDnX - 1) / kDnX, ((uint32_t)a.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
+    hipLaunchKernelGGL(reproject_pass, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist, out_rgba,
+                       out_se);
+    return hipGetLastError();
+}
+
 // The tail tiles' chunk partials (WorkPlan) summed in chunk order (deterministic)
 // into the frame; one thread per tail-tile pixel.  kMom (moment renders): the chunk items' second
 // moments (store_mom's plane) summed in chunk order likewise, into sq.

@@ -27,6 +27,12 @@
 // Alone it renders every sample with moments, in batches of --batch; with --noise-target or --adaptive
 // it filters the frame those loops stop at, and --error-map then holds the filtered standard error.
 // --features FILE writes the first-hit normals as a .raw image (RGB = n * 0.5 + 0.5).
+// --frames N (N > 1, one GPU) renders N views from one resident scene (ptmi_scene_set_camera): frame k's
+// camera is the scene's turned by k x --orbit-step degrees about the world y axis (ptmi/temporal.py
+// orbit_camera: inverse' = rotate_y * inverse, Go's Sin and Cos), its seeds come from --seed + k, and its
+// PNG takes the frame number before the extension (turn.png -> turn.0000.png, ...).  --temporal
+// accumulates across the frames (ptmi_reproject; --max-history N, default 32); --denoise then filters
+// the accumulated frame.
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
 #include <algorithm>
 #include <chrono>
@@ -42,6 +48,7 @@
 
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_host.h"
+#include "geom.h"
 
 namespace {
 
@@ -61,6 +68,9 @@ struct Cfg {
     bool denoise = false, have_iters = false;
     int denoise_iters = 0;  // 0: the library's default
     std::string features;
+    int frames = 1, max_history = 0;  // 0: the library's default
+    bool have_frames = false, have_step = false, temporal = false;
+    double orbit_step = 0.0;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -70,7 +80,7 @@ struct Cfg {
                  "          [--assets DIR] [--out FILE.png] [--raw FILE.raw] [--gpus N] [--split sample|tile]\n"
                  "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n"
                  "          [--adaptive] [--sample-map FILE.raw] [--denoise] [--denoise-iters N]\n"
-                 "          [--features FILE.raw]\n",
+                 "          [--features FILE.raw] [--frames N] [--orbit-step DEGREES] [--temporal] [--max-history N]\n",
                  msg);
     std::exit(2);
 }
@@ -114,6 +124,10 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--denoise") c.denoise = true;
         else if (a == "--denoise-iters") c.denoise_iters = std::atoi(val().c_str()), c.have_iters = true;
         else if (a == "--features") c.features = val();
+        else if (a == "--frames") c.frames = std::atoi(val().c_str()), c.have_frames = true;
+        else if (a == "--orbit-step") c.orbit_step = std::atof(val().c_str()), c.have_step = true;
+        else if (a == "--temporal") c.temporal = true;
+        else if (a == "--max-history") c.max_history = std::atoi(val().c_str());
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
@@ -128,6 +142,18 @@ Cfg parse(int argc, char** argv) {
     if (c.adaptive && !c.have_target) usage("--adaptive needs --noise-target");
     if (!c.sample_map.empty() && !c.adaptive) usage("--sample-map needs --adaptive");
     if (c.adaptive && c.batch < 2) usage("--adaptive needs --batch >= 2");
+    if (c.have_frames && c.frames < 1) usage("--frames must be >= 1");
+    const bool sequence = c.frames > 1;
+    if (c.temporal && !sequence) usage("--temporal needs --frames N with N > 1");
+    if ((c.temporal || sequence) && (c.gpus > 1 || c.adaptive || c.have_target))
+        usage("--frames and --temporal need --gpus 1 and take neither --adaptive nor --noise-target");
+    if (sequence && (!c.raw.empty() || !c.error_map.empty() || !c.features.empty()))
+        usage("--frames writes PNG frames only (no --raw, --error-map or --features)");
+    if (c.have_step && !sequence) usage("--orbit-step needs --frames N with N > 1");
+    if (c.max_history && !c.temporal) usage("--max-history needs --temporal");
+    if (c.temporal && c.max_history && (c.max_history < 1 || c.max_history > 65536)) usage("--max-history must be 1..65536");
+    if (c.max_history < 0) usage("--max-history must be 1..65536");
+    if (c.temporal && c.samples < 2) usage("--temporal needs --samples >= 2 (the variance of a frame)");
     if (c.batch <= 0 || (c.have_target && !(c.noise_target >= 0.0))) usage("--batch must be positive, --noise-target >= 0");
     return c;
 }
@@ -282,6 +308,100 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
     return rc;
 }
 
+// "turn.png" -> "turn.0007.png"
+std::string frame_name(const std::string& png, int k) {
+    char num[16];
+    std::snprintf(num, sizeof(num), ".%04d", k);
+    const size_t dot = png.rfind('.'), slash = png.rfind('/');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return png + num;
+    return png.substr(0, dot) + num + png.substr(dot);
+}
+
+// --frames: N views of one resident scene (ptmi/temporal.py render_sequence in C).  Per frame k:
+// ptmi_scene_set_camera(the camera turned by k * orbit_step), seeds from stream_seed + k, a moment render
+// of every sample, the error map, finalize, and -- with --temporal or --denoise -- the feature pass, the
+// accumulation against frame k - 1 (history and records ping-pong) and the filter.  One PNG per frame.
+int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, uint64_t stream_seed,
+                  const std::string& png, char* err, size_t err_len) {
+    const size_t n = (size_t)c.width * c.height;
+    const uint32_t W = (uint32_t)c.width, H = (uint32_t)c.height, samples = (uint32_t)c.samples;
+    ptmi_scene* sc = nullptr;
+    int rc = ptmi_scene_create_textured(c.device_index, r.objects, r.n_obj, r.triangles, r.n_tri, r.groups, r.n_grp,
+                                        r.camera, tex, &sc, err, err_len);
+    if (rc) return rc;
+    double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *se = nullptr, *stats = nullptr, *image = nullptr,
+           *acc = nullptr, *acc_se = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr;
+    double *feat[2] = {nullptr, nullptr}, *hist[2] = {nullptr, nullptr};
+    auto hip = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return false;
+        std::snprintf(err, err_len, "%s failed: %s", what, hipGetErrorString(e));
+        rc = PTMI_ERR_HIP;
+        return true;
+    };
+    auto dmalloc = [&](double** p, size_t doubles) { return hip(hipMalloc((void**)p, doubles * sizeof(double)), "hipMalloc"); };
+    const bool guides = c.temporal || c.denoise;
+    const size_t wb = ptmi_denoise_work_bytes(W, H);
+    std::vector<double> out(n * 4);
+    unsigned char cam0[PTMI_CAMERA_BYTES], cam[PTMI_CAMERA_BYTES], prev_cam[PTMI_CAMERA_BYTES];
+    std::memcpy(cam0, r.camera, sizeof(cam0));
+    ptmi_host::Mat inv0;
+    std::memcpy(inv0.data(), cam0 + 56, sizeof(double) * 16);  // CLCamera.inverse (ocltracer.go:85-96)
+    do {
+        if (hip(hipSetDevice(c.device_index), "hipSetDevice")) break;
+        if (dmalloc(&seeds, n) || dmalloc(&sums, n * 4) || dmalloc(&sq, n) || dmalloc(&se, n) || dmalloc(&stats, 4) ||
+            dmalloc(&image, n * 4))
+            break;
+        if (guides && (dmalloc(&feat[0], n * PTMI_FEATURE_DOUBLES) || dmalloc(&feat[1], n * PTMI_FEATURE_DOUBLES))) break;
+        if (c.temporal && (dmalloc(&hist[0], n * PTMI_HISTORY_DOUBLES) || dmalloc(&hist[1], n * PTMI_HISTORY_DOUBLES) ||
+                           dmalloc(&acc, n * 4) || dmalloc(&acc_se, n)))
+            break;
+        if (c.denoise && (dmalloc(&dn_out, n * 4) || dmalloc(&dn_se, n) || hip(hipMalloc((void**)&dn_work, wb), "hipMalloc")))
+            break;
+        for (int k = 0; k < c.frames && !rc; k++) {
+            std::memcpy(cam, cam0, sizeof(cam));
+            const ptmi_host::Mat rot = ptmi_host::rotate_y(((double)k * c.orbit_step) * M_PI / 180.0);
+            const ptmi_host::Mat inv = ptmi_host::multiply(rot, inv0);
+            std::memcpy(cam + 56, inv.data(), sizeof(double) * 16);
+            if ((rc = ptmi_scene_set_camera(sc, cam, err, err_len))) break;
+            if ((rc = ptmi_fill_seeds(seeds, (uint32_t)n, stream_seed + (uint64_t)k, nullptr, err, err_len))) break;
+            if ((rc = ptmi_scene_render_moments(sc, samples, 0, samples, 1, 0, seeds, sums, sq, 0, nullptr, err, err_len)))
+                break;
+            if ((rc = ptmi_error_map(sums, sq, W, H, se, nullptr, stats, nullptr, err, err_len))) break;
+            if ((rc = ptmi_finalize(sums, image, (uint32_t)n, samples, nullptr, err, err_len))) break;
+            const double *frame = image, *frame_se = se;
+            double* f = feat[k & 1];
+            if (guides && (rc = ptmi_scene_features(sc, f, nullptr, err, err_len))) break;
+            if (c.temporal) {
+                ptmi_reproject_params rp{32, 0, 0.9, 0.02, 0.05};
+                if (c.max_history) rp.max_history = (uint32_t)c.max_history;
+                if ((rc = ptmi_reproject(image, se, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
+                                         k ? prev_cam : nullptr, W, H, &rp, hist[k & 1], acc, acc_se, nullptr, err,
+                                         err_len)))
+                    break;
+                frame = acc;
+                frame_se = acc_se;
+            }
+            if (c.denoise) {
+                ptmi_denoise_params dp{5, PTMI_DENOISE_DEMODULATE, 4.0, 0.01, 7, 0};
+                if (c.denoise_iters) dp.iterations = (uint32_t)c.denoise_iters;
+                if ((rc = ptmi_denoise(frame, frame_se, f, W, H, &dp, dn_out, dn_se, dn_work, wb, nullptr, err, err_len)))
+                    break;
+                frame = dn_out;
+            }
+            if (hip(hipMemcpy(out.data(), frame, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy")) break;
+            std::memcpy(prev_cam, cam, sizeof(cam));
+            const std::string name = frame_name(png, k);
+            if ((rc = ptmi_host_write_png(name.c_str(), out.data(), c.width, c.height, err, err_len))) break;
+            std::fprintf(stderr, "frame %d (%.6g degrees): wrote %s\n", k, (double)k * c.orbit_step, name.c_str());
+        }
+    } while (false);
+    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, feat[0], feat[1], hist[0],
+                      hist[1]})
+        if (p) (void)hipFree(p);
+    ptmi_scene_destroy(sc);
+    return rc;
+}
+
 bool known_scene(const std::string& s) {
     const std::string names = ptmi_host_scene_names();
     size_t a = 0;
@@ -340,6 +460,22 @@ int main(int argc, char** argv) {
     double rel_err = 0.0;
     std::vector<double> counts_rgba;
     uint32_t tiles_at_max = 0;
+    const std::string png = c.out.empty() ? "out-" + std::to_string(c.samples) + "-" + std::to_string(c.width) +
+                                                     "x" + std::to_string(c.height) + ".png"
+                                               : c.out;
+    if (c.frames > 1) {  // a camera sequence: its frames are written as they finish
+        rc = render_frames(c, r, textured ? &tex : nullptr, stream, png, err, sizeof(err));
+        ptmi_host_free_records(&r);
+        ptmi_host_free_textures(&tex);
+        if (rc) {
+            std::fprintf(stderr, "sequence render failed (%d): %s\n", rc, err);
+            return 1;
+        }
+        const double trace_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+        std::fprintf(stderr, "scene %s: %d frames of %dx%d x %d spp in %.3f s\n", scene.c_str(), c.frames, c.width,
+                     c.height, c.samples, trace_s);
+        return 0;
+    }
     if (noise) {
         rc = render_noise(c, r, textured ? &tex : nullptr, stream, out, se_rgba, samples_done, rel_err, counts_rgba,
                           tiles_at_max, normals_rgba, err, sizeof(err));
@@ -361,9 +497,6 @@ int main(int argc, char** argv) {
         return 1;
     }
     const auto t2 = std::chrono::steady_clock::now();
-    const std::string png = c.out.empty() ? "out-" + std::to_string(c.samples) + "-" + std::to_string(c.width) + "x" +
-                                                std::to_string(c.height) + ".png"
-                                          : c.out;
     if ((rc = ptmi_host_write_png(png.c_str(), out.data(), c.width, c.height, err, sizeof(err)))) {
         std::fprintf(stderr, "%s\n", err);
         return 1;

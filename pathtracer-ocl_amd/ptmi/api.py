@@ -39,8 +39,9 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_trace_multi_timed", "ptmi_sample_split_point", "ptmi_combine_frames",
            "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate",
            "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts", "ptmi_scene_features",
-           "ptmi_denoise", "ptmi_denoise_work_bytes")
+           "ptmi_denoise", "ptmi_denoise_work_bytes", "ptmi_scene_set_camera", "ptmi_reproject")
 FEATURE_DOUBLES = 12    # PTMI_FEATURE_DOUBLES: doubles per pixel of Scene.features
+HISTORY_DOUBLES = 8     # PTMI_HISTORY_DOUBLES: doubles per pixel of a reproject history
 DENOISE_DEMODULATE = 1  # PTMI_DENOISE_DEMODULATE
 
 
@@ -60,6 +61,15 @@ class DenoiseParams(ctypes.Structure):
 
     def __init__(self, iterations=5, flags=DENOISE_DEMODULATE, sigma_l=4.0, sigma_d=0.01, normal_power=7):
         super().__init__(iterations, flags, sigma_l, sigma_d, normal_power, 0)
+
+
+class ReprojectParams(ctypes.Structure):
+    """ptmi_reproject_params (include/ptmi.h); the constructor's defaults are the library's."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("normal_cos", ctypes.c_double),
+                ("plane_dist", ctypes.c_double), ("min_weight", ctypes.c_double)]
+
+    def __init__(self, max_history=32, flags=0, normal_cos=0.9, plane_dist=0.02, min_weight=0.05):
+        super().__init__(max_history, flags, normal_cos, plane_dist, min_weight)
 
 
 class PtmiError(RuntimeError):
@@ -131,6 +141,15 @@ def load_library(path=None):
         lib.ptmi_denoise_work_bytes.argtypes = [u32, u32]
         lib.ptmi_denoise.restype = i32
         lib.ptmi_denoise.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(DenoiseParams), vp, vp, vp, sz, vp, cp, sz]
+    if hasattr(lib, "ptmi_reproject"):  # (likewise)
+        lib.ptmi_scene_set_camera.restype = i32
+        lib.ptmi_scene_set_camera.argtypes = [vp, vp, cp, sz]
+        lib.ptmi_reproject.restype = i32
+        lib.ptmi_reproject.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(ReprojectParams), vp, vp, vp,
+                                       vp, cp, sz]
+    if hasattr(lib, "ptmi_diag_scene_tile_cost"):
+        lib.ptmi_diag_scene_tile_cost.restype = i32
+        lib.ptmi_diag_scene_tile_cost.argtypes = [vp, vp, u32, cp, sz]
     lib.ptmi_finalize.restype = i32
     lib.ptmi_finalize.argtypes = [vp, vp, u32, u32, vp, cp, sz]
     lib.ptmi_fill_seeds.restype = i32
@@ -357,6 +376,27 @@ class Scene:
         _check(self._lib.ptmi_scene_features(self._h, ctypes.c_void_p(feat_ptr or None), ctypes.c_void_p(stream), err,
                                              len(err)), err)
 
+    def set_camera(self, camera_record):
+        """ptmi_scene_set_camera: a new 256-byte camera record of the scene's width and height.  The scene
+        then renders bit for bit what a scene freshly created with this camera renders; only the camera
+        is converted and uploaded.  Blocks until the device's earlier work and the upload are done."""
+        cam = np.ascontiguousarray(np.asarray(camera_record).reshape(1))
+        if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
+            raise TypeError("camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
+                                                                          cam.dtype.itemsize))
+        err = ctypes.create_string_buffer(512)
+        _check(self._lib.ptmi_scene_set_camera(self._h, _ptr(cam), err, len(err)), err)
+
+    def tile_cost(self):
+        """ptmi_diag_scene_tile_cost: the static dispatch class (0..9) of every 8x8 tile as the scene's
+        next ordered render sees it, raster order (all 0 without meshes)."""
+        tiles = ((self.width + 7) // 8) * ((self.height + 7) // 8)
+        out = np.zeros(tiles, dtype=np.uint8)
+        err = ctypes.create_string_buffer(256)
+        _check(self._lib.ptmi_diag_scene_tile_cost(self._h, out.ctypes.data_as(ctypes.c_void_p), tiles, err, len(err)),
+               err)
+        return out
+
     def set_rng(self, mode):
         """RNG_NOISE3D (default, the reference's noise3D bit for bit) or RNG_XOSHIRO (the
         opt-in statistical mode: images converge to the same expectation, not equal)."""
@@ -492,3 +532,36 @@ def denoise(rgba_ptr, se_ptr, feat_ptr, w, h, out_ptr, out_se_ptr=0, params=None
                                        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_ptr or None),
                                        ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(work.data_ptr()),
                                        work.numel() * work.element_size(), ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def reproject_params(params=None):
+    """A ReprojectParams from None (the defaults), a ReprojectParams or a dict of some of its fields."""
+    if params is None or isinstance(params, ReprojectParams):
+        return params
+    return ReprojectParams(**dict(params))
+
+
+def reproject(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_camera, w, h, out_hist_ptr,
+              out_rgba_ptr=0, out_se_ptr=0, params=None, stream=0):
+    """ptmi_reproject: temporal accumulation of a W x H frame in device memory -- this frame (rgba_ptr,
+    se_ptr, feat_ptr) blended into the previous frame's history (prev_hist_ptr, W*H*HISTORY_DOUBLES;
+    0 = first frame) found through prev_feat_ptr and prev_camera (the previous frame's camera record,
+    host memory).  out_hist_ptr gets the new history (no output may overlap an input or another output), out_rgba_ptr /
+    out_se_ptr (optional) the accumulated frame and its standard error, as denoise() takes them.
+    params: None, a ReprojectParams or a dict of its fields.  The operation order is ptmi/temporal.py
+    reproject_reference."""
+    p = reproject_params(params)
+    cam = None
+    if prev_camera is not None:
+        cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
+        if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
+            raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
+                                                                               cam.dtype.itemsize))
+    err = ctypes.create_string_buffer(512)
+    _check(load_library().ptmi_reproject(ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None),
+                                         ctypes.c_void_p(feat_ptr or None), ctypes.c_void_p(prev_hist_ptr or None),
+                                         ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
+                                         ctypes.byref(p) if p is not None else None,
+                                         ctypes.c_void_p(out_hist_ptr or None), ctypes.c_void_p(out_rgba_ptr or None),
+                                         ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(stream), err, len(err)),
+           err)
