@@ -46,6 +46,16 @@ int ptmi_diag_tile_cost(const void* objects, uint32_t n_obj, const void* triangl
  * next ordered render sorts by (after ptmi_scene_set_camera: the new view's).  Host only. */
 int ptmi_diag_scene_tile_cost(ptmi_scene* s, uint8_t* out, uint32_t n_out, char* err, size_t err_len);
 
+/* The candidate masks of the camera-ray stage (csrc/ptmi_camcull.h), one
+ * uint32 per 8x8 tile in raster order: bit i (i < 16) plane i of the scene's plane list, bit 16 + i its
+ * i-th scale+translate sphere; a cleared bit: no camera ray of the tile can record that object.
+ * ptmi_diag_tile_cull copies a resident scene's masks (its current camera's) into out[0 .. tiles);
+ * ptmi_diag_tile_cull_host computes them on the host from the records (no device call). */
+int ptmi_diag_tile_cull(ptmi_scene* s, uint32_t* out, size_t n_tiles);
+int ptmi_diag_tile_cull_host(const void* objects, uint32_t n_obj, const void* triangles, uint32_t n_tri,
+                             const void* groups, uint32_t n_grp, const void* camera, uint32_t* out, size_t n_tiles,
+                             char* err, size_t err_len);
+
 /* Mesh-scene execution form (study build; the product has only the one-kernel form and
  * returns PTMI_ERR_UNSUPPORTED for enable != 0): enable != 0 renders affine mesh scenes in
  * the split form (trace_split_kernel + walk_split_kernel, pass by pass), 0 (the default)

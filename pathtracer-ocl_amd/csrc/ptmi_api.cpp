@@ -22,6 +22,7 @@
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_diag.h"
 #include "ptmi_bvh.h"
+#include "ptmi_camcull.h"
 #include "ptmi_device.h"
 #include "ptmi_f16.h"
 
@@ -746,7 +747,7 @@ int upload_scene(const HostScene& hs, int device_index, const ptmi_textures* tex
     {  // the camera record in device memory (ptmi_kernels.hip camera_ptr)
         // and, behind it, the camera terms of this scene's planes and spheres (ptmi_device.h), computed
         // from the record just uploaded: they go with every upload of the camera record
-        SCENE_TRY(hipMalloc(&s->buffers[14], cam_record_bytes(s->dev.n_planes, s->dev.n_spheres_st)));
+        SCENE_TRY(hipMalloc(&s->buffers[14], cam_record_bytes(s->dev.n_planes, s->dev.n_spheres_st, hs.cam.width, hs.cam.height)));
         SCENE_TRY(hipMemcpy(s->buffers[14], &hs.cam, sizeof(DevCamera), hipMemcpyHostToDevice));
         s->dev.camg = (const DevCamera*)s->buffers[14];
         SCENE_TRY(launch_camera_terms(s->dev, nullptr));
@@ -1989,6 +1990,55 @@ extern "C" int ptmi_diag_scene_tile_cost(ptmi_scene* s, uint8_t* out, uint32_t n
     } else {
         std::memset(out, 0, tiles);
     }
+    return PTMI_OK;
+}
+
+// The tiles' candidate masks of a resident scene, read back from behind its camera terms.
+extern "C" int ptmi_diag_tile_cull(ptmi_scene* s, uint32_t* out, size_t n_tiles) {
+    if (!s || !out) return PTMI_ERR_ARG;
+    const size_t tiles = cam_tiles((int32_t)s->width, (int32_t)s->height);
+    if (n_tiles < tiles) return PTMI_ERR_ARG;
+    if (hipSetDevice(s->device) != hipSuccess) return PTMI_ERR_HIP;
+    const uint32_t* src = cull_masks(s->dev.camg, s->dev.n_planes, s->dev.n_spheres_st);
+    return hipMemcpy(out, src, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess ? PTMI_OK : PTMI_ERR_HIP;
+}
+
+// The same masks from the classifier's host build (no device call): the records prepare_scene makes,
+// the camera terms by find_closest_prims' expressions (its recording form, CAM 2) in host doubles.
+extern "C" int ptmi_diag_tile_cull_host(const void* objects, uint32_t n_obj, const void* triangles, uint32_t n_tri,
+                                        const void* groups, uint32_t n_grp, const void* camera, uint32_t* out,
+                                        size_t n_tiles, char* err, size_t err_len) {
+    if (!out) {
+        set_err(err, err_len, "out == NULL");
+        return PTMI_ERR_ARG;
+    }
+    HostScene hs;
+    const int rc = prepare_scene(objects, n_obj, triangles, n_tri, groups, n_grp, camera, nullptr, hs, err, err_len);
+    if (rc) return rc;
+    const size_t tiles = cam_tiles(hs.cam.width, hs.cam.height);
+    if (n_tiles < tiles) {
+        set_err(err, err_len, "out holds %zu tiles, the frame has %zu", n_tiles, tiles);
+        return PTMI_ERR_ARG;
+    }
+    const double* co = hs.cam.origin;
+    const int np = (int)hs.planes.size(), nq = (int)hs.spheres.size(), npy2 = hs.n_planes_y & ~1;
+    std::vector<double> cpl((size_t)np), csp((size_t)kCamSphere * nq);
+    for (int p = 0; p < np; p++) {
+        const double* m = hs.planes[p].row1;
+        cpl[p] = p < npy2 ? m[1] * co[1] + m[3] : ((m[0] * co[0] + m[1] * co[1]) + m[2] * co[2]) + m[3];
+    }
+    for (int q = 0; q < nq; q++) {
+        const SphereRec& Q = hs.spheres[q];
+        double* t = &csp[(size_t)kCamSphere * q];
+        t[0] = Q.m0 * co[0] + Q.m3;
+        t[1] = Q.m5 * co[1] + Q.m7;
+        t[2] = Q.m10 * co[2] + Q.m11;
+        t[3] = std::fma(t[2], t[2], std::fma(t[1], t[1], t[0] * t[0])) - 1.0;
+    }
+    const int tiles_x = (hs.cam.width + 7) / 8;
+    for (size_t t = 0; t < tiles; t++)
+        out[t] = cull_tile_mask(hs.cam, hs.planes.data(), np, hs.spheres.data(), nq, cpl.data(), csp.data(),
+                                (int)(t % (size_t)tiles_x), (int)(t / (size_t)tiles_x));
     return PTMI_OK;
 }
 

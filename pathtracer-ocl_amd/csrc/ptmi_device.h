@@ -186,9 +186,14 @@ struct DevScene {
 // by-value DevScene -- every kernel's argument layout -- stays as it is:
 //   cam_planes  [n_planes]         indexed like DevScene::planes: the origin term of the plane's row-1 sum
 //   cam_spheres [n_spheres_st][4]  indexed like DevScene::spheres: M origin + t (x, y, z), c = |.|^2 - 1
+//   cull_masks  [tiles]            uint32 per 8x8 tile, raster order (work_item's tile index): the planes
+//                                  (bits 0-15) and st spheres (bits 16-31) a camera ray of the tile can
+//                                  record as a candidate (ptmi_camcull.h; tile_cull_pass, every upload)
 constexpr int kCamSphere = 4;
-inline size_t cam_record_bytes(int32_t n_planes, int32_t n_spheres_st) {
-    return sizeof(DevCamera) + ((size_t)n_planes + (size_t)kCamSphere * (size_t)n_spheres_st) * sizeof(double);
+inline size_t cam_tiles(int32_t width, int32_t height) { return (size_t)((width + 7) / 8) * (size_t)((height + 7) / 8); }
+inline size_t cam_record_bytes(int32_t n_planes, int32_t n_spheres_st, int32_t width, int32_t height) {
+    return sizeof(DevCamera) + ((size_t)n_planes + (size_t)kCamSphere * (size_t)n_spheres_st) * sizeof(double) +
+           cam_tiles(width, height) * sizeof(uint32_t);
 }
 static_assert(sizeof(DevCamera) % sizeof(double) == 0, "the terms follow the record as doubles");
 

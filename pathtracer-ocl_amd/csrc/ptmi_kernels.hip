@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "ptmi_device.h"
+#include "ptmi_camcull.h"
 #include "ptmi_sinf.h"
 #include "ptmi_fp64core.h"
 
@@ -24,6 +25,12 @@
 // design; the product is always built with PTMI_ABLATE == 0.
 #ifndef PTMI_ABLATE
 #define PTMI_ABLATE 0
+#endif
+// PTMI_CAM_CULL: 1 (the product) -- the camera-ray stage of the lockstep kernels without DoF tests only the
+// planes and scale+translate spheres its tile's mask keeps (ptmi_camcull.h; find_closest_prims' masked
+// form); 0 -- the stage tests every object (A/B; the masks are still computed and ignored).
+#ifndef PTMI_CAM_CULL
+#define PTMI_CAM_CULL 1
 #endif
 // PTMI_STATS: DIAGNOSTIC builds -- 1 (make stats): tallies traversal events into
 // ptmi_stats[] (read with ptmi_stats_read); 2 (make timers): per-wave phase clocks
@@ -1082,10 +1089,17 @@ __device__ __forceinline__ void plane_rows_nz(M m, d4 ro, d4 rd, double& oy, dou
 // CAM (cam_term): 1 -- ro is the scene camera's origin (the lockstep loop's first bounce without DoF):
 // the origin terms of the planes and the scale+translate spheres come from the scene's tables and only
 // the direction half is computed; everything from plane_q / sphere_quad's a, b, disc on is the same code.
+// cmask (CAM 1, PTMI_CAM_CULL): the tile's candidate mask (ptmi_camcull.h), wave-uniform.  ~0: the loops
+// below as they are.  Otherwise every plane and st sphere of the scene has a bit, and only those whose bit
+// is set are tested -- each by the expressions the loops use for it, planes in list order, so the
+// candidates it drops are none and the winner, the lexicographic minimum of (t, key), is the same.
 template <int FL, int CAM = 0>
-__device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 rd) {
+__device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 rd, [[maybe_unused]] uint32_t cmask = ~0u) {
     constexpr bool A = !(FL & F_PROJ);
     static_assert(CAM == 0 || A, "camera terms: affine kernels");
+    constexpr bool kCull = CAM == 1 && PTMI_CAM_CULL != 0;
+    [[maybe_unused]] bool culled = false;
+    if constexpr (kCull) culled = cmask != ~0u;
     Hit h{1024.0, -1, -1, -1, 0.0, 0.0};
     // the camera terms behind the camera record (ptmi_device.h): cam_planes, cam_spheres
     [[maybe_unused]] const double* const cpl = CAM ? (const double*)(S.camg + 1) : nullptr;
@@ -1096,7 +1110,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
     // every object).  Duplicate-free: the last iteration re-loads its own record.
     // Planes come first, in increasing list index, so inside the plane loop a tie in
     // t can never favour the later plane: strict t < h.t is better() there.
-    const int np = (PTMI_ABLATE & 8) ? 0 : S.n_planes;
+    const int np = ((PTMI_ABLATE & 8) || culled) ? 0 : S.n_planes;  // culled: the masked walk below instead
     // intersectPlane (478-483): row 1 only.  Planes are taken two at a time so the
     // two independent division chains overlap (then one odd plane).
     // Row 1 of mul() for the plane's origin and direction (intersectPlane, 478-483).
@@ -1134,13 +1148,51 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         h.t = c ? q : h.t;
         h.pk = c ? pack_hit(P.slot, P.key) : h.pk;
     };
+    if constexpr (kCull) {
+        if (culled) {
+            // The kept planes in list order, two at a time (two independent division chains), then an odd
+            // one.  A plane of the leading floor / ceiling pairs (index below n_planes_y rounded down to
+            // even) has dy = m1 rd.y (plane_rows_nz<2>; in a parallel pair the partner's m1 is the same
+            // bits), every other plane the full direction row; oy is the table's; plane_q is div_core,
+            // bit-identical to plane_q2's shared reciprocal.
+            const int npy2 = ((PTMI_ABLATE & 512) ? 0 : S.n_planes_y) & ~1;
+            auto kept_t = [&](int i, const auto& P, double& q, bool& ok) {
+                double oy, dy;
+                if (i < npy2) plane_rows_nz<2, CAM>(P.row1, ro, rd, oy, dy, cpl, i);
+                else plane_rows(P, oy, dy, i);
+                plane_q(oy, dy, q, ok);
+            };
+            uint32_t pm = cmask & ((1u << S.n_planes) - 1u);  // (n_planes <= 16 here)
+            while (pm & (pm - 1u)) {
+                const int i0 = __builtin_ctz(pm);
+                pm &= pm - 1u;
+                const int i1 = __builtin_ctz(pm);
+                pm &= pm - 1u;
+                const auto &P0 = cmem(S.planes)[i0], &P1 = cmem(S.planes)[i1];
+                double q0, q1;
+                bool k0, k1;
+                kept_t(i0, P0, q0, k0);
+                kept_t(i1, P1, q1, k1);
+                plane_take(P0, q0, k0);
+                plane_take(P1, q1, k1);
+            }
+            if (pm) {
+                const int i0 = __builtin_ctz(pm);
+                const auto& P0 = cmem(S.planes)[i0];
+                double q0;
+                bool k0;
+                kept_t(i0, P0, q0, k0);
+                plane_take(P0, q0, k0);
+            }
+        }
+    }
     int p = 0;
     // Affine scenes: the leading planes whose row 1 is (+-0, m1, +-0, m3) -- floors and
     // ceilings, S.n_planes_y of them in list order -- skip the +-0 terms (plane_rows_nz).
     // (Dispatching every plane, or every run of planes, on its zero pattern measured
     // slower: C2 +4-6 %.)
     if constexpr (A) {
-        const int npy = (PTMI_ABLATE & 512) ? 0 : S.n_planes_y;  // DIAGNOSTIC 512: full rows for all
+        const int npy = ((PTMI_ABLATE & 512) || culled) ? 0 : S.n_planes_y;  // DIAGNOSTIC 512: full rows for all
         for (; p + 1 < npy; p += 2) {
             PTMI_WADD(47, 1ull);
             const auto &P0 = cmem(S.planes)[p], &P1 = cmem(S.planes)[p + 1];
@@ -1191,7 +1243,7 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         plane_t(P0, q0, k0, p);
         plane_take(P0, q0, k0);
     }
-    const int nq = (PTMI_ABLATE & 16) ? 0 : S.n_spheres_st;
+    const int nq = ((PTMI_ABLATE & 16) || culled) ? 0 : S.n_spheres_st;  // culled: the masked walk below
     auto sphere_ray = [&](const auto& Q, d4& o, d4& d, [[maybe_unused]] const double* ct) {
         if constexpr (A) {
             if constexpr (CAM == 1) {
@@ -1287,6 +1339,24 @@ __device__ __forceinline__ Hit find_closest_prims(const DevScene& S, d4 ro, d4 r
         double a0, b0, disc0;
         sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * q);
         defer(a0, b0, disc0, Q0.slot, Q0.key);  // (q >= 2 here: the first sphere is peeled)
+    }
+    if constexpr (kCull) {
+        if (culled) {  // the kept st spheres: the first as `first`, the others deferred, as above
+            uint32_t qm = (cmask >> 16) & ((1u << S.n_spheres_st) - 1u);
+            bool head = true;
+            while (qm) {
+                const int i = __builtin_ctz(qm);
+                qm &= qm - 1u;
+                const auto& Q0 = cmem(S.spheres)[i];
+                d4 o0, d0;
+                sphere_ray(Q0, o0, d0, csp + kCamSphere * i);
+                double a0, b0, disc0;
+                sphere_quad<A, CAM>(o0, d0, a0, b0, disc0, csp + kCamSphere * i);
+                if (head) first(a0, b0, disc0, Q0.slot, Q0.key);
+                else defer(a0, b0, disc0, Q0.slot, Q0.key);
+                head = false;
+            }
+        }
     }
     if (pend) {
         PTMI_WADD(33, 1ull);
@@ -2646,6 +2716,14 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
     // The item's sample range is the same for every lane of the wave.
     const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)it.c0);
     const uint32_t c1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)it.c1);
+    // The tile's candidate mask of the camera-ray stage (ptmi_camcull.h), behind the camera terms: one
+    // scalar load per item, by the tile's raster index whichever way the plan named the tile.
+    [[maybe_unused]] uint32_t cmask = ~0u;
+    if constexpr (PTMI_CAM_CULL != 0 && !kDof) {
+        const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (it.py / kTile) * ((S0.cam.width + kTile - 1) / kTile) + it.px / kTile);
+        cmask = cmem(cull_masks(S0.camg, S0.n_planes, S0.n_spheres_st))[tile];
+    }
     // colors (tracer.cl:1179) and the current path's accumColor: one LDS slot per lane each, as in
     // trace_kernel's regeneration loop (volatile: really in LDS, not promoted to VGPRs).
     __shared__ double acc_lds[3 * kBlock];
@@ -2707,6 +2785,7 @@ __device__ __forceinline__ void trace_lockstep(const DevScene& S0, uint32_t samp
                 PTMI_WADD(46, (unsigned long long)__popcll(__ballot(1)));
                 Hit h;
                 if (P.dead) h.pk = -1;
+                else if constexpr (CAM == 1) h = find_closest_prims<FL, CAM>(S, P.ro, P.rd, cmask);
                 else h = find_closest_prims<FL, CAM>(S, P.ro, P.rd);
                 PTMI_TADD(13, t_b);
                 PTMI_TSTAMP(t_d);
@@ -3028,8 +3107,27 @@ __global__ void camera_terms_pass(DevScene S) {
     (void)find_closest_prims<0, 2>(S, mk(co[0], co[1], co[2], 1.0), mk(0.0, 0.0, -1.0, 0.0));
 }
 
+// The tiles' candidate masks (ptmi_camcull.h) behind the terms just written, one thread per tile: the
+// classifier on the record, the plane / sphere records and the terms in device memory.
+static_assert(kCullEps == kEps, "the classifier's EPSILON is the kernels'");
+__global__ void tile_cull_pass(DevScene S) {
+    const int tiles_x = (S.cam.width + kTile - 1) / kTile, tiles_y = (S.cam.height + kTile - 1) / kTile;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint32_t)(tiles_x * tiles_y)) return;
+    const double* cpl = (const double*)(S.camg + 1);
+    uint32_t* out = const_cast<uint32_t*>(cull_masks(S.camg, S.n_planes, S.n_spheres_st));
+    out[t] = cull_tile_mask(*S.camg, S.planes, S.n_planes, S.spheres, S.n_spheres_st, cpl, cpl + S.n_planes,
+                            (int)(t % (uint32_t)tiles_x), (int)(t / (uint32_t)tiles_x));
+}
+
+// Both passes on one stream, in order: no host synchronisation between them.
 hipError_t launch_camera_terms(const DevScene& S, hipStream_t st) {
     hipLaunchKernelGGL(camera_terms_pass, dim3(1), dim3(64), 0, st, S);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t tiles = (uint32_t)cam_tiles(S.cam.width, S.cam.height);
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(tile_cull_pass, dim3((tiles + 63) / 64), dim3(64), 0, st, S);
     return hipGetLastError();
 }
 

@@ -150,6 +150,11 @@ def load_library(path=None):
     if hasattr(lib, "ptmi_diag_scene_tile_cost"):
         lib.ptmi_diag_scene_tile_cost.restype = i32
         lib.ptmi_diag_scene_tile_cost.argtypes = [vp, vp, u32, cp, sz]
+    if hasattr(lib, "ptmi_diag_tile_cull"):
+        lib.ptmi_diag_tile_cull.restype = i32
+        lib.ptmi_diag_tile_cull.argtypes = [vp, vp, sz]
+        lib.ptmi_diag_tile_cull_host.restype = i32
+        lib.ptmi_diag_tile_cull_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, sz, cp, sz]
     lib.ptmi_finalize.restype = i32
     lib.ptmi_finalize.argtypes = [vp, vp, u32, u32, vp, cp, sz]
     lib.ptmi_fill_seeds.restype = i32
@@ -285,6 +290,20 @@ def index_stats(objects, triangles, groups, camera):
                     list(out)))
 
 
+def tile_cull_host(objects, triangles, groups, camera):
+    """ptmi_diag_tile_cull_host (host only): the camera-ray stage's candidate mask of every 8x8 tile,
+    raster order -- bit i plane i, bit 16 + i scale+translate sphere i; all ones where nothing is culled."""
+    objects, triangles, groups, camera = _records(objects, triangles, groups, camera)
+    rec = camera.view(layout.CAMERA_DTYPE)
+    w, h = int(rec["width"][0]), int(rec["height"][0])
+    out = np.zeros(((w + 7) // 8) * ((h + 7) // 8), dtype=np.uint32)
+    err = ctypes.create_string_buffer(1024)
+    _check(load_library().ptmi_diag_tile_cull_host(_ptr(objects), len(objects), _ptr(triangles), len(triangles),
+                                                   _ptr(groups), len(groups), _ptr(camera),
+                                                   out.ctypes.data_as(ctypes.c_void_p), len(out), err, len(err)), err)
+    return out
+
+
 class force_flags:
     """Context manager (ptmi_diag_force_flags): scenes created inside it -- by Trace or
     Scene -- launch the kernel instantiation `flags` instead of their own (test hook for
@@ -395,6 +414,14 @@ class Scene:
         err = ctypes.create_string_buffer(256)
         _check(self._lib.ptmi_diag_scene_tile_cost(self._h, out.ctypes.data_as(ctypes.c_void_p), tiles, err, len(err)),
                err)
+        return out
+
+    def tile_cull(self):
+        """ptmi_diag_tile_cull: the scene's candidate masks (tile_cull_host's layout) as the device holds
+        them for its current camera."""
+        out = np.zeros(((self.width + 7) // 8) * ((self.height + 7) // 8), dtype=np.uint32)
+        rc = self._lib.ptmi_diag_tile_cull(self._h, out.ctypes.data_as(ctypes.c_void_p), len(out))
+        _check(rc, ctypes.create_string_buffer(b"ptmi_diag_tile_cull failed"))
         return out
 
     def set_rng(self, mode):
