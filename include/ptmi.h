@@ -345,7 +345,8 @@ int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* fea
  * an unchanged camera are the same estimate, and averaging them halves nothing.
  * The guides are the pinhole ray through the pixel centre: the first hit on glass or a mirror
  * reprojects the glass, not what shows through it, and view-dependent shading lags by the history
- * length; the scene is static, only the camera moves; at 1 spp se is +inf and every pixel resets.
+ * length; the objects are taken to stand still, only the camera moves (ptmi_reproject_motion follows
+ * objects that moved); at 1 spp se is +inf and every pixel resets.
  * Allocates nothing; asynchronous on the stream.  No output may overlap an input or another output, in
  * whole or in part (callers ping-pong two history buffers; there is no in-place form: out_rgba_dev is
  * not rgba_dev, out_se_dev is not se_dev); the ranges are checked.  Every buffer but se_dev and
@@ -408,6 +409,73 @@ int ptmi_scene_set_rng(ptmi_scene* s, int mode, char* err, size_t err_len);
  * HOST-BLOCKING: the call waits for all earlier work of the device (renders in flight read the camera
  * record in device memory) and returns after the upload and the terms pass have completed. */
 int ptmi_scene_set_camera(ptmi_scene* s, const void* camera, char* err, size_t err_len);
+
+/* New object records (n_obj * 1024-byte CLObject) on a resident scene: objects move, turn, change colour
+ * or material between frames without a new traversal index.  Afterwards the scene is what
+ * ptmi_scene_create gives for these objects with the scene's own triangles, groups, camera and textures:
+ * every later render, moment render, tile render and feature pass is bit-identical to the fresh scene's.
+ * May change: transform, inverse and inverse_transpose (taken from the record as given, as at creation),
+ * colour, emission, reflectivity, refractive index, min_y / max_y and the texture fields.  Must NOT
+ * change: n_obj, each object's type, and for a group object childCount, its child roots and bb_min /
+ * bb_max (the traversal index of a mesh is built from them, in the group's own space; the transform is
+ * not part of it): PTMI_ERR_ARG.  Re-derived, by the code the create call runs: the device objects and
+ * their plane normals, the compact plane and sphere records, the kernel instantiation (materials, affine
+ * or not, textured -- objects can move a scene between instantiations), the camera terms and the tiles'
+ * candidate masks, and for mesh scenes the tile classes and the dispatch order.  In the statistical RNG
+ * mode objects that make the scene non-affine or textured are PTMI_ERR_UNSUPPORTED.  Everything is
+ * checked before anything changes: after PTMI_ERR_ARG or PTMI_ERR_UNSUPPORTED the scene renders exactly
+ * as before.  PTMI_ERR_HIP (a runtime call failed during the update) may leave the records, the flags
+ * and the terms partly updated: set the objects again, or destroy the scene.  (A flag set forced with
+ * ptmi_diag_force_flags stays the one the scene was created under.)
+ * HOST-BLOCKING, as ptmi_scene_set_camera: the call waits for all earlier work of the device and returns
+ * after the uploads and the passes have completed. */
+int ptmi_scene_set_objects(ptmi_scene* s, const void* objects, uint32_t n_obj, char* err, size_t err_len);
+
+/*
+ * How each object moved between two frames, for ptmi_reproject_motion: from the previous and the current
+ * object records (HOST pointers, n_obj * 1024 bytes each, the same objects in the same order) into
+ * motion_dev, n_obj * PTMI_MOTION_DOUBLES doubles of device memory, 16-byte aligned.  Record k belongs to
+ * object k of the caller's list -- the id of the first-hit records:
+ *   [0..12)   rows 0-2 of B = prev.transform * cur.inverse: a current world point -> where that surface
+ *             point was in the previous frame
+ *   [12..21)  G = L(prev.inverse_transpose) * L(cur.transform)^T (L: the upper-left 3 x 3), row-major:
+ *             the same map for normals (unnormalised)
+ *   [21]      0.0 static: the 384 bytes of transform, inverse and inverse_transpose are equal in both
+ *             records;  2.0 no history: the bottom row of cur.inverse or of prev.transform is not
+ *             (0, 0, 0, 1), or an entry of B or G is not finite;  otherwise 1.0 moved
+ *   [22..24)  0
+ * The products are computed on the host, each entry as ((a0 b0 + a1 b1) + a2 b2) + a3 b3, separately
+ * rounded (ptmi/temporal.py motion_matrices states them).  PTMI_ERR_ARG before any device call for a NULL
+ * pointer, n_obj outside 1..16 or a misaligned buffer.  The copy runs in stream order; the call returns
+ * when it is done (it may block the host).
+ */
+#define PTMI_MOTION_DOUBLES 24
+int ptmi_motion_table(const void* prev_objects, const void* cur_objects, uint32_t n_obj, double* motion_dev,
+                      void* hip_stream, char* err, size_t err_len);
+
+/*
+ * ptmi_reproject for scenes whose objects move (ptmi_scene_set_objects): motion_dev is the table
+ * ptmi_motion_table wrote for the previous and the current frame's objects, n_obj its length (1..16).
+ * Per pixel with a first hit on object k = its record's id:
+ *   static (state 0), or k outside [0, n_obj): exactly ptmi_reproject's path -- with an all-static table
+ *     every output equals ptmi_reproject's bit for bit;
+ *   no history (state 2): the pixel resets;
+ *   moved (state 1):  x' = B (x_p, 1), each row ((b0 x + b1 y) + b2 z) + b3;  m = G n_p, each row
+ *     (g0 n.x + g1 n.y) + g2 n.z;  l = (m0^2 + m1^2) + m2^2, the pixel resets unless l > 0 and finite;
+ *     n' = m / sqrt(l).  x' is projected with the previous camera, and the taps are tested with
+ *     n' . n_q >= normal_cos and |n' . (x_q - x')| <= plane_dist * t_p.  The blend is ptmi_reproject's.
+ * Rigid and affine motions of whole objects are followed.  Only what the first-hit records carry is:
+ * shadows, reflections and indirect light that move with an object lag by the history length, and
+ * geometry inside a mesh does not deform.  The exact operation order is ptmi/temporal.py
+ * reproject_reference with `motion`.  All of ptmi_reproject's rules and argument checks apply; the motion
+ * table is one more input no output may overlap, and must be 16-byte aligned.
+ */
+int ptmi_reproject_motion(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                          const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
+                          uint32_t width, uint32_t height, const ptmi_reproject_params* params /* NULL = defaults */,
+                          double* out_hist_dev, double* out_rgba_dev /* may be NULL */,
+                          double* out_se_dev /* may be NULL */, const double* motion_dev, uint32_t n_obj,
+                          void* hip_stream, char* err, size_t err_len);
 
 /* Kernel timing: with timing enabled, every trace_kernel launch of the scene is
  * bracketed by HIP events recorded on the launch stream; ptmi_scene_kernel_time

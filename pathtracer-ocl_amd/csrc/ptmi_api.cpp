@@ -25,6 +25,7 @@
 #include "ptmi_camcull.h"
 #include "ptmi_device.h"
 #include "ptmi_f16.h"
+#include "ptmi_motion.h"
 
 // DIAGNOSTIC study build (make study): the split execution form, the standalone walk
 // kernels and the measured tile order (ptmi_kernels.hip PTMI_STUDY).  The product has 0.
@@ -58,7 +59,7 @@ hipError_t launch_denoise(const double* rgba, const double* se, const double* fe
                           double* out_se, double* work, int variant, hipStream_t st);
 hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
                             const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
-                            double* out_se, hipStream_t st);
+                            double* out_se, const double* motion, int32_t n_obj, hipStream_t st);
 const void* trace_kernel_symbol(int flags);
 bool tile_list_supported(int flags);
 int trace_kernel_flags(int flags);
@@ -96,6 +97,7 @@ struct TileCostInput {
 struct SceneFlagBasis {
     int obj_bits = 0;       // F_GROUPS | F_CYLCUBE | F_MATERIALS
     bool affine = true;     // every object and triangle normal passes the affine test below
+    bool tris_affine = true;  // the triangles' share of `affine` (they never change on a resident scene)
     bool textured = false;  // the one textured instantiation
     int forced = -1;        // ptmi_diag_force_flags at creation (-1: none)
     int wide = 0;           // F_WIDE
@@ -139,6 +141,13 @@ struct ptmi_scene {
     uint32_t width = 0, height = 0;
     int flags = 0;  // scene features -> kernel instantiation (ptmi_kernels.hip F_*)
     SceneFlagBasis basis;  // what `flags` takes from everything but the camera (ptmi_scene_set_camera)
+    // ptmi_scene_set_objects: the converted list as uploaded (type runs, each group's RootRec slot in
+    // child_base), the caller's records' identity fields, and the sizes of the two allocations that follow
+    // the number of scale+translate spheres
+    std::vector<DevObject> objs_host;
+    std::vector<ObjectIdentity> identity;
+    uint32_t n_grp = 0;
+    size_t sphere_bytes = 0, cam_bytes = 0;  // allocated: buffers[6], buffers[14]
     int hemi_mismatch = 0;  // hemisphere-table records where affine and generic sequences differ (upload_scene)
     int rng = PTMI_RNG_NOISE3D;  // ptmi_scene_set_rng: PTMI_RNG_XOSHIRO launches the F_XRNG instantiations
     bool timing = false;
@@ -252,6 +261,62 @@ int convert_camera(const uint8_t* camera, DevCamera& cam, char* err, size_t err_
     return PTMI_OK;
 }
 
+// One 1024-byte CLObject record -> DevObject (everything but its place in the scene: child_base, and for
+// a group the RootRec slot that replaces its roots): the one conversion behind ptmi_scene_create and
+// ptmi_scene_set_objects, so both give the kernels the same bits.  A group's child_count is the record's.
+int convert_object(const uint8_t* b, uint32_t i, uint32_t n_grp, DevObject& o, char* err, size_t err_len) {
+    std::memset(&o, 0, sizeof o);
+    o.key = (int32_t)i;
+    std::memcpy(o.inv, b + 128, 128);
+    std::memcpy(o.inv_t, b + 256, 128);
+    std::memcpy(o.color, b + 384, 32);
+    std::memcpy(o.emission, b + 416, 32);
+    o.refractive_index = rd<double>(b + 448);
+    const int64_t type = rd<int64_t>(b + 456);
+    o.type = (type >= 0 && type <= 4) ? (int32_t)type : 999;
+    o.min_y = rd<double>(b + 464);
+    o.max_y = rd<double>(b + 472);
+    o.reflectivity = rd<double>(b + 480);
+    std::memcpy(o.bb_min, b + 520, 32);
+    o.st = is_st_pattern(o.inv) ? 1 : 0;
+    o.invt_diag = is_diag3(o.inv_t) ? 1 : 0;
+    std::memcpy(o.bb_max, b + 552, 32);
+    o.tex = b[844] ? 1 : 0;  // isTextured, textureIndex, isTexturedNM, textureIndexNM (ocltracer.go:44-47)
+    o.tex_index = b[845];
+    o.tex_nm = b[846] ? 1 : 0;
+    o.tex_index_nm = b[847];
+    std::memcpy(o.tex_scale, b + 488, 32);  // textureScaleX, Y, XNM, YNM (ocltracer.go:36-39)
+    o.child_count = 0;
+    if (o.type == 4) {
+        const int32_t cc = rd<int32_t>(b + 584);
+        if (cc < 0 || cc > 64) {
+            set_err(err, err_len, "object %u: childCount %d out of range", i, cc);
+            return PTMI_ERR_ARG;
+        }
+        for (int32_t c = 0; c < cc; c++) {
+            const int32_t r = rd<int32_t>(b + 588 + 4 * c);
+            if (r < 0 || (uint32_t)r >= n_grp) {
+                set_err(err, err_len, "object %u: child root %d outside %u groups", i, r, n_grp);
+                return PTMI_ERR_ARG;
+            }
+        }
+        o.child_count = cc;
+    }
+    return PTMI_OK;
+}
+
+// Intersectable objects in type runs [planes | spheres | cylinders | cubes |
+// groups], list order inside a run.  Types > 4 and groups without BVH roots
+// can never record an intersection (tracer.cl:551-720) and are left out.
+void sort_into_runs(const std::vector<DevObject>& all, std::vector<DevObject>& objs, int32_t run_end[5]) {
+    objs.clear();
+    for (int t = 0; t < 5; t++) {
+        for (const DevObject& o : all)
+            if (o.type == t && (t != 4 || o.child_count > 0)) objs.push_back(o);
+        run_end[t] = (int32_t)objs.size();
+    }
+}
+
 int convert_scene(const uint8_t* objects, uint32_t n_obj, const uint8_t* tris, uint32_t n_tri, const uint8_t* groups,
                   uint32_t n_grp, const uint8_t* camera, std::vector<DevObject>& objs, std::vector<int32_t>& roots,
                   std::vector<DevNode>& nodes, RootIndex& index, std::vector<RootRec>& root_rec,
@@ -270,55 +335,11 @@ int convert_scene(const uint8_t* objects, uint32_t n_obj, const uint8_t* tris, u
     for (uint32_t i = 0; i < n_obj; i++) {
         const uint8_t* b = objects + (size_t)PTMI_OBJECT_BYTES * i;
         DevObject& o = all[i];
-        std::memset(&o, 0, sizeof o);
-        o.key = (int32_t)i;
-        std::memcpy(o.inv, b + 128, 128);
-        std::memcpy(o.inv_t, b + 256, 128);
-        std::memcpy(o.color, b + 384, 32);
-        std::memcpy(o.emission, b + 416, 32);
-        o.refractive_index = rd<double>(b + 448);
-        const int64_t type = rd<int64_t>(b + 456);
-        o.type = (type >= 0 && type <= 4) ? (int32_t)type : 999;
-        o.min_y = rd<double>(b + 464);
-        o.max_y = rd<double>(b + 472);
-        o.reflectivity = rd<double>(b + 480);
-        std::memcpy(o.bb_min, b + 520, 32);
-        o.st = is_st_pattern(o.inv) ? 1 : 0;
-        o.invt_diag = is_diag3(o.inv_t) ? 1 : 0;
-        std::memcpy(o.bb_max, b + 552, 32);
-        o.tex = b[844] ? 1 : 0;  // isTextured, textureIndex, isTexturedNM, textureIndexNM (ocltracer.go:44-47)
-        o.tex_index = b[845];
-        o.tex_nm = b[846] ? 1 : 0;
-        o.tex_index_nm = b[847];
-        std::memcpy(o.tex_scale, b + 488, 32);  // textureScaleX, Y, XNM, YNM (ocltracer.go:36-39)
-        o.child_count = 0;
+        if (const int rc = convert_object(b, i, n_grp, o, err, err_len)) return rc;
         o.child_base = (int32_t)roots.size();
-        if (o.type == 4) {
-            const int32_t cc = rd<int32_t>(b + 584);
-            if (cc < 0 || cc > 64) {
-                set_err(err, err_len, "object %u: childCount %d out of range", i, cc);
-                return PTMI_ERR_ARG;
-            }
-            for (int32_t c = 0; c < cc; c++) {
-                const int32_t r = rd<int32_t>(b + 588 + 4 * c);
-                if (r < 0 || (uint32_t)r >= n_grp) {
-                    set_err(err, err_len, "object %u: child root %d outside %u groups", i, r, n_grp);
-                    return PTMI_ERR_ARG;
-                }
-                roots.push_back(r);
-            }
-            o.child_count = cc;
-        }
+        for (int32_t c = 0; c < o.child_count; c++) roots.push_back(rd<int32_t>(b + 588 + 4 * c));
     }
-    // Intersectable objects in type runs [planes | spheres | cylinders | cubes |
-    // groups], list order inside a run.  Types > 4 and groups without BVH roots
-    // can never record an intersection (tracer.cl:551-720) and are left out.
-    objs.clear();
-    for (int t = 0; t < 5; t++) {
-        for (const DevObject& o : all)
-            if (o.type == t && (t != 4 || o.child_count > 0)) objs.push_back(o);
-        run_end[t] = (int32_t)objs.size();
-    }
+    sort_into_runs(all, objs, run_end);
     nodes.resize(n_grp);
     std::vector<int32_t> tri_off(n_grp), tri_cnt(n_grp);
     for (uint32_t g = 0; g < n_grp; g++) {
@@ -430,7 +451,73 @@ struct HostScene {
     int32_t leaf_bit = kLeafNarrow;  // Node4 child code format (finalize_index_codes)
     uint32_t n_list = 0, n_grp = 0, n_tri = 0;
     int32_t n_planes_y = 0;
+    std::vector<ObjectIdentity> identity;  // per record of the caller's list (ptmi_scene_set_objects)
 };
+
+// What the flags take from the objects (the converted list) and the triangles: obj_bits, affine, textured.
+// The one derivation behind ptmi_scene_create and ptmi_scene_set_objects.
+void object_flag_basis(const std::vector<DevObject>& objs, bool tris_affine, SceneFlagBasis& fb) {
+    fb.obj_bits = 0;
+    fb.affine = true;
+    fb.textured = false;
+    for (const DevObject& o : objs) {
+        if (o.type == 4) fb.obj_bits |= 1;                                    // F_GROUPS
+        if (o.type == 2 || o.type == 3) fb.obj_bits |= 2;                     // F_CYLCUBE
+        if (o.reflectivity != 0.0 || o.refractive_index != 1.0) fb.obj_bits |= 4;  // F_MATERIALS
+    }
+    for (const DevObject& o : objs)
+        fb.affine = fb.affine && o.inv[12] == 0.0 && o.inv[13] == 0.0 && o.inv[14] == 0.0 && o.inv[15] == 1.0 &&
+                    o.inv_t[3] == 0.0 && o.inv_t[7] == 0.0 && o.inv_t[11] == 0.0;
+    fb.affine = fb.affine && tris_affine;
+    for (const DevObject& o : objs)
+        if (o.type == 1) fb.affine = fb.affine && tame(o.inv);
+    // Textured plane/sphere/cube colours or plane normal maps: the one textured
+    // instantiation (generic arithmetic + software sampler, tracer.cl:907-914, 1077-1092).
+    for (const DevObject& o : objs)
+        if ((o.tex && (o.type == 0 || o.type == 1 || o.type == 3)) || (o.tex_nm && o.type == 0)) fb.textured = true;
+}
+
+// The compact plane / scale+translate sphere records (ptmi_device.h) of a converted object list, with
+// the planes' pairing: likewise shared by create and update.
+void compact_records(const std::vector<DevObject>& objs, std::vector<PlaneRec>& planes, std::vector<SphereRec>& spheres,
+                     int32_t& n_planes_y) {
+    planes.clear();
+    spheres.clear();
+    for (size_t k = 0; k < objs.size(); k++) {
+        const DevObject& o = objs[k];
+        if (o.type == 0) {
+            PlaneRec r{};
+            std::memcpy(r.row1, o.inv + 4, 32);
+            r.slot = (int32_t)k;
+            r.key = o.key;
+            r.nz = (r.row1[0] != 0.0 ? 1 : 0) | (r.row1[1] != 0.0 ? 2 : 0) | (r.row1[2] != 0.0 ? 4 : 0);
+            planes.push_back(r);
+        } else if (o.type == 1 && o.st) {
+            SphereRec r{};
+            r.m0 = o.inv[0];
+            r.m3 = o.inv[3];
+            r.m5 = o.inv[5];
+            r.m7 = o.inv[7];
+            r.m10 = o.inv[10];
+            r.m11 = o.inv[11];
+            r.m15 = o.inv[15];
+            r.slot = (int32_t)k;
+            r.key = o.key;
+            spheres.push_back(r);
+        }
+    }
+    // The leading planes (list order kept) whose row 1 has +-0 x and z entries, and the
+    // parallel pairs (identical row1[0..2]) as the affine plane loops pair the planes:
+    // (0,1), (2,3), ... below n_planes_y, then on from there (find_closest_prims).
+    const int np = (int)planes.size();
+    int npy = 0;
+    while (npy < np && planes[npy].row1[0] == 0.0 && planes[npy].row1[2] == 0.0) npy++;
+    n_planes_y = npy;
+    auto same = [&](int a, int b) { return std::memcmp(planes[a].row1, planes[b].row1, 24) == 0; };
+    int p = 0;
+    for (; p + 1 < npy; p += 2) planes[p].par = same(p, p + 1);
+    for (; p + 1 < np; p += 2) planes[p].par = same(p, p + 1);
+}
 
 int prepare_scene(const void* objects, uint32_t n_obj, const void* triangles, uint32_t n_tri, const void* groups,
                   uint32_t n_grp, const void* camera, const ptmi_textures* textures, HostScene& hs, char* err,
@@ -441,29 +528,17 @@ int prepare_scene(const void* objects, uint32_t n_obj, const void* triangles, ui
     if (rc) return rc;
     hs.leaf_bit = finalize_index_codes(hs.index, hs.root_rec);
     // What the flags take from the objects, the triangles and the force hook (SceneFlagBasis); the camera's
-    // part is scene_flags', which ptmi_scene_set_camera runs again.
+    // part is scene_flags', which ptmi_scene_set_camera runs again, the objects' part object_flag_basis',
+    // which ptmi_scene_set_objects runs again.
     SceneFlagBasis& fb = hs.basis;
     fb = SceneFlagBasis{};
-    for (const DevObject& o : hs.objs) {
-        if (o.type == 4) fb.obj_bits |= 1;                                    // F_GROUPS
-        if (o.type == 2 || o.type == 3) fb.obj_bits |= 2;                     // F_CYLCUBE
-        if (o.reflectivity != 0.0 || o.refractive_index != 1.0) fb.obj_bits |= 4;  // F_MATERIALS
-    }
-    for (const DevObject& o : hs.objs)
-        fb.affine = fb.affine && o.inv[12] == 0.0 && o.inv[13] == 0.0 && o.inv[14] == 0.0 && o.inv[15] == 1.0 &&
-                    o.inv_t[3] == 0.0 && o.inv_t[7] == 0.0 && o.inv_t[11] == 0.0;
     for (const DevTriShade& t : hs.st)
-        fb.affine = fb.affine && std::isfinite(t.n1[3]) && std::isfinite(t.n2[3]) && std::isfinite(t.n3[3]);
-    for (const DevObject& o : hs.objs)
-        if (o.type == 1) fb.affine = fb.affine && tame(o.inv);
+        fb.tris_affine = fb.tris_affine && std::isfinite(t.n1[3]) && std::isfinite(t.n2[3]) && std::isfinite(t.n3[3]);
+    object_flag_basis(hs.objs, fb.tris_affine, fb);
     // Child codes past 16 bits (>= 2^15 Node4s or triangles): a traversal stack of 32-bit
     // entries -- the affine F_WIDE instantiation (ptmi_kernels.hip trace_groups), or the
     // generic one for non-affine scenes (round 5 sent every such scene to the generic one).
     fb.wide = hs.leaf_bit != kLeafNarrow ? 256 : 0;                           // F_WIDE
-    // Textured plane/sphere/cube colours or plane normal maps: the one textured
-    // instantiation (generic arithmetic + software sampler, tracer.cl:907-914, 1077-1092).
-    for (const DevObject& o : hs.objs)
-        if ((o.tex && (o.type == 0 || o.type == 1 || o.type == 3)) || (o.tex_nm && o.type == 0)) fb.textured = true;
     fb.forced = g_force_flags.load();  // ptmi_diag_force_flags (tests): one load
     const int flags = scene_flags(fb, hs.cam);
     if (textures) {
@@ -480,43 +555,10 @@ int prepare_scene(const void* objects, uint32_t n_obj, const void* triangles, ui
         }
     }
     hs.flags = flags;
-    // compact plane / scale+translate sphere records (ptmi_device.h)
-    for (size_t k = 0; k < hs.objs.size(); k++) {
-        const DevObject& o = hs.objs[k];
-        if (o.type == 0) {
-            PlaneRec r{};
-            std::memcpy(r.row1, o.inv + 4, 32);
-            r.slot = (int32_t)k;
-            r.key = o.key;
-            r.nz = (r.row1[0] != 0.0 ? 1 : 0) | (r.row1[1] != 0.0 ? 2 : 0) | (r.row1[2] != 0.0 ? 4 : 0);
-            hs.planes.push_back(r);
-        } else if (o.type == 1 && o.st) {
-            SphereRec r{};
-            r.m0 = o.inv[0];
-            r.m3 = o.inv[3];
-            r.m5 = o.inv[5];
-            r.m7 = o.inv[7];
-            r.m10 = o.inv[10];
-            r.m11 = o.inv[11];
-            r.m15 = o.inv[15];
-            r.slot = (int32_t)k;
-            r.key = o.key;
-            hs.spheres.push_back(r);
-        }
-    }
-    // The leading planes (list order kept) whose row 1 has +-0 x and z entries, and the
-    // parallel pairs (identical row1[0..2]) as the affine plane loops pair the planes:
-    // (0,1), (2,3), ... below n_planes_y, then on from there (find_closest_prims).
-    {
-        const int np = (int)hs.planes.size();
-        int npy = 0;
-        while (npy < np && hs.planes[npy].row1[0] == 0.0 && hs.planes[npy].row1[2] == 0.0) npy++;
-        hs.n_planes_y = npy;
-        auto same = [&](int a, int b) { return std::memcmp(hs.planes[a].row1, hs.planes[b].row1, 24) == 0; };
-        int p = 0;
-        for (; p + 1 < npy; p += 2) hs.planes[p].par = same(p, p + 1);
-        for (; p + 1 < np; p += 2) hs.planes[p].par = same(p, p + 1);
-    }
+    compact_records(hs.objs, hs.planes, hs.spheres, hs.n_planes_y);
+    hs.identity.resize(n_obj);
+    for (uint32_t i = 0; i < n_obj; i++)
+        hs.identity[i] = object_identity((const uint8_t*)objects + (size_t)PTMI_OBJECT_BYTES * i);
     hs.n_list = n_obj;
     hs.n_grp = n_grp;
     hs.n_tri = n_tri;
@@ -669,6 +711,10 @@ int upload_scene(const HostScene& hs, int device_index, const ptmi_textures* tex
         T.h = (int32_t)textures->height[k];
         T.layers = (int32_t)textures->count[k];
     }
+    s->objs_host = hs.objs;
+    s->identity = hs.identity;
+    s->n_grp = hs.n_grp;
+    s->sphere_bytes = std::max<size_t>(hs.spheres.size() * sizeof(SphereRec), 256);  // as upload() sized it
     s->dev.objs = (const DevObject*)s->buffers[0];
     for (int t = 0; t < 5; t++) s->dev.run_end[t] = hs.run_end[t];
     s->dev.planes = (const PlaneRec*)s->buffers[5];
@@ -747,7 +793,8 @@ int upload_scene(const HostScene& hs, int device_index, const ptmi_textures* tex
     {  // the camera record in device memory (ptmi_kernels.hip camera_ptr)
         // and, behind it, the camera terms of this scene's planes and spheres (ptmi_device.h), computed
         // from the record just uploaded: they go with every upload of the camera record
-        SCENE_TRY(hipMalloc(&s->buffers[14], cam_record_bytes(s->dev.n_planes, s->dev.n_spheres_st, hs.cam.width, hs.cam.height)));
+        s->cam_bytes = cam_record_bytes(s->dev.n_planes, s->dev.n_spheres_st, hs.cam.width, hs.cam.height);
+        SCENE_TRY(hipMalloc(&s->buffers[14], s->cam_bytes));
         SCENE_TRY(hipMemcpy(s->buffers[14], &hs.cam, sizeof(DevCamera), hipMemcpyHostToDevice));
         s->dev.camg = (const DevCamera*)s->buffers[14];
         SCENE_TRY(launch_camera_terms(s->dev, nullptr));
@@ -1468,6 +1515,127 @@ int ptmi_scene_set_camera(ptmi_scene* s, const void* camera, char* err, size_t e
     return PTMI_OK;
 }
 
+int ptmi_scene_set_objects(ptmi_scene* s, const void* objects, uint32_t n_obj, char* err, size_t err_len) {
+    if (!s || !objects) {
+        set_err(err, err_len, "ptmi_scene_set_objects: scene or objects == NULL");
+        return PTMI_ERR_ARG;
+    }
+    // Everything is checked before anything changes: after an error the scene renders as before.
+    if (n_obj != s->identity.size()) {
+        set_err(err, err_len, "ptmi_scene_set_objects: %u objects on a scene of %zu (the list keeps its length)", n_obj,
+                s->identity.size());
+        return PTMI_ERR_ARG;
+    }
+    const uint8_t* recs = (const uint8_t*)objects;
+    std::vector<DevObject> all(n_obj), objs;
+    for (uint32_t i = 0; i < n_obj; i++) {
+        const uint8_t* b = recs + (size_t)PTMI_OBJECT_BYTES * i;
+        if (const char* what = identity_change(s->identity[i], object_identity(b))) {
+            set_err(err, err_len, "ptmi_scene_set_objects: object %u changes its %s (the traversal index and the "
+                                  "object runs were built from it: create a new scene)", i, what);
+            return PTMI_ERR_ARG;
+        }
+        if (const int rc = convert_object(b, i, s->n_grp, all[i], err, err_len)) return rc;
+    }
+    int32_t run_end[5];
+    sort_into_runs(all, objs, run_end);
+    // equal types and child counts give the slots of the resident list: each keeps its place in the scene
+    if (objs.size() != s->objs_host.size()) {
+        set_err(err, err_len, "ptmi_scene_set_objects: %zu intersectable objects, the scene has %zu", objs.size(),
+                s->objs_host.size());
+        return PTMI_ERR_ARG;
+    }
+    for (size_t k = 0; k < objs.size(); k++) {
+        if (objs[k].key != s->objs_host[k].key || objs[k].type != s->objs_host[k].type) {
+            set_err(err, err_len, "ptmi_scene_set_objects: slot %zu holds another object", k);
+            return PTMI_ERR_ARG;
+        }
+        objs[k].child_base = s->objs_host[k].child_base;    // groups: the RootRec slot
+        objs[k].child_count = s->objs_host[k].child_count;  // (1 for a group, see convert_scene)
+    }
+    SceneFlagBasis basis = s->basis;  // (forced, wide and the triangles' share stay)
+    object_flag_basis(objs, basis.tris_affine, basis);
+    const int flags = scene_flags(basis, s->dev.cam);
+    if (s->rng == PTMI_RNG_XOSHIRO && (flags & (16 | 32))) {  // F_PROJ | F_TEX, as ptmi_scene_set_rng
+        set_err(err, err_len, "the statistical RNG mode exists for affine, untextured scenes only (these objects make "
+                              "the scene %s)", (flags & 32) ? "textured" : "not affine");
+        return PTMI_ERR_UNSUPPORTED;
+    }
+    std::vector<PlaneRec> planes;
+    std::vector<SphereRec> spheres;
+    int32_t n_planes_y = 0;
+    compact_records(objs, planes, spheres, n_planes_y);
+    if ((int32_t)planes.size() != s->dev.n_planes) {  // (the types are the scene's: cannot happen)
+        set_err(err, err_len, "ptmi_scene_set_objects: %zu planes, the scene has %d", planes.size(), s->dev.n_planes);
+        return PTMI_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // renders in flight read the records in device memory
+    // The scale+translate sphere records and the camera allocation (its terms and masks follow the
+    // record) grow with the number of such spheres: a sphere that loses a rotation adds one.
+    const size_t sphere_bytes = spheres.size() * sizeof(SphereRec);
+    if (sphere_bytes > s->sphere_bytes) {
+        void* grown = nullptr;
+        HIP_TRY(hipMalloc(&grown, sphere_bytes));
+        (void)hipFree(s->buffers[6]);
+        s->buffers[6] = grown;
+        s->sphere_bytes = sphere_bytes;
+        s->dev.spheres = (const SphereRec*)grown;
+    }
+    const size_t cam_bytes = cam_record_bytes(s->dev.n_planes, (int32_t)spheres.size(), s->dev.cam.width, s->dev.cam.height);
+    if (cam_bytes > s->cam_bytes) {
+        void* grown = nullptr;
+        HIP_TRY(hipMalloc(&grown, cam_bytes));
+        (void)hipFree(s->buffers[14]);
+        s->buffers[14] = grown;
+        s->cam_bytes = cam_bytes;
+        s->dev.camg = (const DevCamera*)grown;
+        HIP_TRY(hipMemcpy(s->buffers[14], &s->dev.cam, sizeof(DevCamera), hipMemcpyHostToDevice));
+    }
+    if (!objs.empty()) {
+        HIP_TRY(hipMemcpy(s->buffers[0], objs.data(), objs.size() * sizeof(DevObject), hipMemcpyHostToDevice));
+        HIP_TRY(launch_plane_normals((DevObject*)s->buffers[0], (int)objs.size(), nullptr));
+    }
+    if (!planes.empty())
+        HIP_TRY(hipMemcpy(s->buffers[5], planes.data(), planes.size() * sizeof(PlaneRec), hipMemcpyHostToDevice));
+    if (!spheres.empty()) HIP_TRY(hipMemcpy(s->buffers[6], spheres.data(), sphere_bytes, hipMemcpyHostToDevice));
+    s->dev.n_planes_y = n_planes_y;
+    s->dev.n_spheres_st = (int32_t)spheres.size();
+    s->objs_host = objs;
+    s->basis = basis;
+    s->flags = flags;
+    // the camera terms and the tiles' candidate masks: from the records just uploaded
+    HIP_TRY(launch_camera_terms(s->dev, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(resident_waves(s));  // the instantiation may have changed (F_MATERIALS, F_PROJ, F_TEX)
+    if (s->flags & 1) {  // mesh scenes: the group objects' inverses behind the tile classes
+        size_t j = 0;
+        for (int k = run_end[3]; k < run_end[4] && j < s->tc_in.objs.size(); k++, j++)
+            std::memcpy(s->tc_in.objs[j].inv, objs[k].inv, sizeof(s->tc_in.objs[j].inv));
+        s->tile_cost.clear();
+        s->order_n = 0;
+    }
+    return PTMI_OK;
+}
+
+int ptmi_motion_table(const void* prev_objects, const void* cur_objects, uint32_t n_obj, double* motion_dev,
+                      void* hip_stream, char* err, size_t err_len) {
+    if (!prev_objects || !cur_objects || !motion_dev || n_obj == 0 || n_obj > PTMI_MAX_OBJECTS ||
+        ((uintptr_t)motion_dev & 15u)) {
+        set_err(err, err_len, "bad motion table arguments (%u objects; NULL or misaligned pointer)", n_obj);
+        return PTMI_ERR_ARG;
+    }
+    double table[PTMI_MAX_OBJECTS * PTMI_MOTION_DOUBLES];
+    for (uint32_t k = 0; k < n_obj; k++)
+        motion_record((const uint8_t*)prev_objects + (size_t)PTMI_OBJECT_BYTES * k,
+                      (const uint8_t*)cur_objects + (size_t)PTMI_OBJECT_BYTES * k, table + PTMI_MOTION_DOUBLES * k);
+    // In stream order behind the work that still reads the buffer; `table` lives until the copy is done.
+    const size_t bytes = (size_t)n_obj * PTMI_MOTION_DOUBLES * sizeof(double);  // (outside HIP_TRY: its message quotes the call)
+    HIP_TRY(hipMemcpyAsync(motion_dev, table, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
 // The world-to-camera matrix of a camera record: the FP64 cofactor inverse of its `inverse`
 // (ptmi/temporal.py cofactor_inverse states the same operations).  false: singular or not finite.
 static bool cofactor_inverse(const double* m, double* out) {
@@ -1496,10 +1664,12 @@ static bool cofactor_inverse(const double* m, double* out) {
     return true;
 }
 
-int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* prev_hist_dev,
-                   const double* prev_feat_dev, const void* prev_camera, uint32_t width, uint32_t height,
-                   const ptmi_reproject_params* params, double* out_hist_dev, double* out_rgba_dev, double* out_se_dev,
-                   void* hip_stream, char* err, size_t err_len) {
+// ptmi_reproject (motion_dev == NULL, n_obj == 0) and ptmi_reproject_motion: one set of checks.
+static int reproject_checked(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                             const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
+                             uint32_t width, uint32_t height, const ptmi_reproject_params* params,
+                             double* out_hist_dev, double* out_rgba_dev, double* out_se_dev, const double* motion_dev,
+                             uint32_t n_obj, void* hip_stream, char* err, size_t err_len) {
     ptmi_reproject_params p{32, 0, 0.9, 0.02, 0.05};
     if (params) p = *params;
     if (!rgba_dev || !se_dev || !feat_dev || !out_hist_dev || (prev_hist_dev && (!prev_feat_dev || !prev_camera)) ||
@@ -1520,8 +1690,9 @@ int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* f
         const double* p;
         size_t doubles;
     };
-    const Range ins[5] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
-                          {prev_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {prev_feat_dev, npix * PTMI_FEATURE_DOUBLES}};
+    const Range ins[6] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
+                          {prev_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {prev_feat_dev, npix * PTMI_FEATURE_DOUBLES},
+                          {motion_dev, (size_t)n_obj * PTMI_MOTION_DOUBLES}};
     const Range outs[3] = {{out_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {out_rgba_dev, npix * 4}, {out_se_dev, npix}};
     auto overlap = [](const Range& a, const Range& b) {
         if (!a.p || !b.p) return false;
@@ -1530,12 +1701,12 @@ int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* f
     };
     bool aliased = false;
     for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 5; i++) aliased = aliased || overlap(outs[o], ins[i]);
+        for (int i = 0; i < 6; i++) aliased = aliased || overlap(outs[o], ins[i]);
         for (int q = o + 1; q < 3; q++) aliased = aliased || overlap(outs[o], outs[q]);
     }
     if (aliased ||
         (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)prev_hist_dev | (uintptr_t)prev_feat_dev |
-          (uintptr_t)out_hist_dev | (uintptr_t)out_rgba_dev) & 15u)) {
+          (uintptr_t)out_hist_dev | (uintptr_t)out_rgba_dev | (uintptr_t)motion_dev) & 15u)) {
         set_err(err, err_len, "reproject buffers overlap or are not 16-byte aligned");
         return PTMI_ERR_ARG;
     }
@@ -1563,8 +1734,29 @@ int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* f
         a.pixel_size = cam.pixel_size;
     }
     HIP_TRY(launch_reproject(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev, out_rgba_dev,
-                             out_se_dev, (hipStream_t)hip_stream));
+                             out_se_dev, motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
     return PTMI_OK;
+}
+
+int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* prev_hist_dev,
+                   const double* prev_feat_dev, const void* prev_camera, uint32_t width, uint32_t height,
+                   const ptmi_reproject_params* params, double* out_hist_dev, double* out_rgba_dev, double* out_se_dev,
+                   void* hip_stream, char* err, size_t err_len) {
+    return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
+                             out_hist_dev, out_rgba_dev, out_se_dev, nullptr, 0, hip_stream, err, err_len);
+}
+
+int ptmi_reproject_motion(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                          const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
+                          uint32_t width, uint32_t height, const ptmi_reproject_params* params, double* out_hist_dev,
+                          double* out_rgba_dev, double* out_se_dev, const double* motion_dev, uint32_t n_obj,
+                          void* hip_stream, char* err, size_t err_len) {
+    if (!motion_dev || n_obj == 0 || n_obj > PTMI_MAX_OBJECTS) {
+        set_err(err, err_len, "bad reproject arguments (motion table NULL or of %u objects)", n_obj);
+        return PTMI_ERR_ARG;
+    }
+    return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
+                             out_hist_dev, out_rgba_dev, out_se_dev, motion_dev, n_obj, hip_stream, err, err_len);
 }
 
 int ptmi_scene_set_timing(ptmi_scene* s, int enable) {

@@ -3446,6 +3446,15 @@ hipError_t launch_denoise(const double* rgba, const double* se, const double* fe
 // (+ 40 B) out: bandwidth-bound, no LDS.  Every FP64 operation is separately rounded and in the
 // order ptmi/temporal.py reproject_reference states; the matrix, the camera scalars and the
 // thresholds are by-value arguments (scalar registers).
+//
+// kMotion (ptmi_reproject_motion): the pixel's object may have moved since the previous frame.  Its
+// motion record (include/ptmi.h ptmi_motion_table, 192 B) is read per lane by the pixel's id -- ids are
+// not wave-uniform -- as 16-B vector loads; a moved object's point and normal are carried back to where
+// they were (x' = B (x_p, 1), n' = G n_p / |G n_p|) before the projection and the tap tests, a static
+// one (or an id outside the table) takes the path below with the current point, bit for bit, and an
+// object without a usable motion resets.  The instantiation without kMotion ignores the two trailing
+// arguments and keeps the instruction stream it had as a plain kernel.
+template <bool kMotion>
 __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __restrict__ rgba,
                                                                 const double* __restrict__ se,
                                                                 const double* __restrict__ feat,
@@ -3453,7 +3462,8 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
                                                                 const double* __restrict__ prev_feat,
                                                                 ReprojectArgs a, double* __restrict__ out_hist,
                                                                 double* __restrict__ out_rgba,
-                                                                double* __restrict__ out_se) {
+                                                                double* __restrict__ out_se,
+                                                                const double* __restrict__ motion, int n_obj) {
     const int W = a.W, H = a.H;
     const int x = (int)blockIdx.x * kDnX + (int)threadIdx.x % kDnX, y = (int)blockIdx.y * kDnY + (int)threadIdx.x / kDnX;
     if (x >= W || y >= H) return;
@@ -3469,11 +3479,38 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
     // the reset: this frame alone (a pixel that is not finite is no history for the next frame)
     double o0 = c0, o1 = c1, o2 = c2, ov = v, on = fin ? 1.0 : 0.0;
     if (prev_hist != nullptr && fin && !(id < 0.0)) {
+        // the surface point and its normal as the previous frame saw them
+        double ux = px, uy = py, uz = pz, m0 = n0, m1 = n1, m2 = n2;
+        bool history = true;
+        if (kMotion) {
+            if (id < (double)n_obj) {  // (id >= 0 here; a NaN id fails and stays static)
+                const double2* mr = reinterpret_cast<const double2*>(motion + 24 * (int)id);
+                const double state = mr[10].y;
+                if (state == 1.0) {
+                    const double2 b0 = mr[0], b1 = mr[1], b2 = mr[2], b3 = mr[3], b4 = mr[4], b5 = mr[5];
+                    const double2 g0 = mr[6], g1 = mr[7], g2 = mr[8], g3 = mr[9], g4 = mr[10];
+                    ux = ((b0.x * px + b0.y * py) + b1.x * pz) + b1.y;
+                    uy = ((b2.x * px + b2.y * py) + b3.x * pz) + b3.y;
+                    uz = ((b4.x * px + b4.y * py) + b5.x * pz) + b5.y;
+                    const double e0 = (g0.x * n0 + g0.y * n1) + g1.x * n2;
+                    const double e1 = (g1.y * n0 + g2.x * n1) + g2.y * n2;
+                    const double e2 = (g3.x * n0 + g3.y * n1) + g4.x * n2;
+                    const double l = (e0 * e0 + e1 * e1) + e2 * e2;
+                    history = l > 0.0 && isfinite(l);
+                    const double len = sqrt(l);
+                    m0 = e0 / len;
+                    m1 = e1 / len;
+                    m2 = e2 / len;
+                } else if (state != 0.0) {
+                    history = false;
+                }
+            }
+        }
         const double* T = a.T;
-        const double qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
-        const double qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-        const double z = -(((T[8] * px + T[9] * py) + T[10] * pz) + T[11]);
-        if (z > 0.0) {
+        const double qx = ((T[0] * ux + T[1] * uy) + T[2] * uz) + T[3];
+        const double qy = ((T[4] * ux + T[5] * uy) + T[6] * uz) + T[7];
+        const double z = -(((T[8] * ux + T[9] * uy) + T[10] * uz) + T[11]);
+        if (history && z > 0.0) {
             const double fu = (a.half_width - qx / z) / a.pixel_size - 0.5;
             const double fv = (a.half_height - qy / z) / a.pixel_size - 0.5;
             const double fx0 = floor(fu), fy0 = floor(fv);
@@ -3493,9 +3530,9 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
                 const double2* fq = reinterpret_cast<const double2*>(prev_feat + 12 * q);
                 const double2 g0 = fq[0], g1 = fq[1], g2 = fq[2], g3 = fq[3];
                 if (g3.y != id) continue;
-                const double dn = (n0 * g2.x + n1 * g2.y) + n2 * g3.x;
+                const double dn = (m0 * g2.x + m1 * g2.y) + m2 * g3.x;
                 if (!(dn >= a.normal_cos)) continue;
-                const double dd = (n0 * (g0.x - px) + n1 * (g0.y - py)) + n2 * (g1.x - pz);
+                const double dd = (m0 * (g0.x - ux) + m1 * (g0.y - uy)) + m2 * (g1.x - uz);
                 if (!(fabs(dd) <= bound)) continue;
                 const double w = (ti ? wx : 1.0 - wx) * (tj ? wy : 1.0 - wy);
                 sw = sw + w;
@@ -3535,10 +3572,14 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
 
 hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
                             const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
-                            double* out_se, hipStream_t st) {
+                            double* out_se, const double* motion, int32_t n_obj, hipStream_t st) {
     const dim3 grid(((uint32_t)a.W + kDnX - 1) / kDnX, ((uint32_t)a.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
-    hipLaunchKernelGGL(reproject_pass, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist, out_rgba,
-                       out_se);
+    if (motion)
+        hipLaunchKernelGGL(reproject_pass<true>, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
+                           out_rgba, out_se, motion, (int)n_obj);
+    else
+        hipLaunchKernelGGL(reproject_pass<false>, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
+                           out_rgba, out_se, motion, 0);
     return hipGetLastError();
 }
 

@@ -32,7 +32,10 @@
 // orbit_camera: inverse' = rotate_y * inverse, Go's Sin and Cos), its seeds come from --seed + k, and its
 // PNG takes the frame number before the extension (turn.png -> turn.0000.png, ...).  --temporal
 // accumulates across the frames (ptmi_reproject; --max-history N, default 32); --denoise then filters
-// the accumulated frame.
+// the accumulated frame.  --move-object I --move-step DX,DY,DZ moves object I of the scene's list along the
+// sequence (ptmi_scene_set_objects): in frame k it carries translate(k * step) * transform with the inverse and
+// inverse transpose of that product (ptmi/temporal.py move_object), and --temporal then follows it
+// (ptmi_motion_table, ptmi_reproject_motion).
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
 #include <algorithm>
 #include <chrono>
@@ -71,6 +74,9 @@ struct Cfg {
     int frames = 1, max_history = 0;  // 0: the library's default
     bool have_frames = false, have_step = false, temporal = false;
     double orbit_step = 0.0;
+    int move_object = -1;
+    bool have_move = false, have_move_step = false;
+    double move_step[3] = {0.0, 0.0, 0.0};
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -80,7 +86,8 @@ struct Cfg {
                  "          [--assets DIR] [--out FILE.png] [--raw FILE.raw] [--gpus N] [--split sample|tile]\n"
                  "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n"
                  "          [--adaptive] [--sample-map FILE.raw] [--denoise] [--denoise-iters N]\n"
-                 "          [--features FILE.raw] [--frames N] [--orbit-step DEGREES] [--temporal] [--max-history N]\n",
+                 "          [--features FILE.raw] [--frames N] [--orbit-step DEGREES] [--temporal] [--max-history N]\n"
+                 "          [--move-object I --move-step DX,DY,DZ]\n",
                  msg);
     std::exit(2);
 }
@@ -127,6 +134,12 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--frames") c.frames = std::atoi(val().c_str()), c.have_frames = true;
         else if (a == "--orbit-step") c.orbit_step = std::atof(val().c_str()), c.have_step = true;
         else if (a == "--temporal") c.temporal = true;
+        else if (a == "--move-object") c.move_object = std::atoi(val().c_str()), c.have_move = true;
+        else if (a == "--move-step") {
+            if (std::sscanf(val().c_str(), "%lf,%lf,%lf", &c.move_step[0], &c.move_step[1], &c.move_step[2]) != 3)
+                usage("--move-step takes DX,DY,DZ");
+            c.have_move_step = true;
+        }
         else if (a == "--max-history") c.max_history = std::atoi(val().c_str());
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
@@ -150,6 +163,9 @@ Cfg parse(int argc, char** argv) {
     if (sequence && (!c.raw.empty() || !c.error_map.empty() || !c.features.empty()))
         usage("--frames writes PNG frames only (no --raw, --error-map or --features)");
     if (c.have_step && !sequence) usage("--orbit-step needs --frames N with N > 1");
+    if ((c.have_move || c.have_move_step) && !sequence) usage("--move-object and --move-step need --frames N with N > 1");
+    if (c.have_move != c.have_move_step) usage("--move-object I and --move-step DX,DY,DZ go together");
+    if (c.have_move && c.move_object < 0) usage("--move-object must be an index into the scene's objects");
     if (c.max_history && !c.temporal) usage("--max-history needs --temporal");
     if (c.temporal && c.max_history && (c.max_history < 1 || c.max_history > 65536)) usage("--max-history must be 1..65536");
     if (c.max_history < 0) usage("--max-history must be 1..65536");
@@ -330,7 +346,7 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
                                         r.camera, tex, &sc, err, err_len);
     if (rc) return rc;
     double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *se = nullptr, *stats = nullptr, *image = nullptr,
-           *acc = nullptr, *acc_se = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr;
+           *acc = nullptr, *acc_se = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr, *motion = nullptr;
     double *feat[2] = {nullptr, nullptr}, *hist[2] = {nullptr, nullptr};
     auto hip = [&](hipError_t e, const char* what) {
         if (e == hipSuccess) return false;
@@ -346,6 +362,15 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
     std::memcpy(cam0, r.camera, sizeof(cam0));
     ptmi_host::Mat inv0;
     std::memcpy(inv0.data(), cam0 + 56, sizeof(double) * 16);  // CLCamera.inverse (ocltracer.go:85-96)
+    // --move-object: the frame's object records (the moved object's three matrices replaced) and the previous frame's
+    const bool moving = c.have_move;
+    const size_t obj_bytes = (size_t)r.n_obj * PTMI_OBJECT_BYTES;
+    std::vector<unsigned char> objs, prev_objs;
+    ptmi_host::Mat transform0 = ptmi_host::identity();
+    if (moving) {
+        objs.assign((const unsigned char*)r.objects, (const unsigned char*)r.objects + obj_bytes);
+        std::memcpy(transform0.data(), objs.data() + (size_t)c.move_object * PTMI_OBJECT_BYTES, sizeof(double) * 16);
+    }
     do {
         if (hip(hipSetDevice(c.device_index), "hipSetDevice")) break;
         if (dmalloc(&seeds, n) || dmalloc(&sums, n * 4) || dmalloc(&sq, n) || dmalloc(&se, n) || dmalloc(&stats, 4) ||
@@ -357,7 +382,20 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             break;
         if (c.denoise && (dmalloc(&dn_out, n * 4) || dmalloc(&dn_se, n) || hip(hipMalloc((void**)&dn_work, wb), "hipMalloc")))
             break;
+        if (moving && c.temporal && dmalloc(&motion, (size_t)PTMI_MOTION_DOUBLES * PTMI_MAX_OBJECTS)) break;
         for (int k = 0; k < c.frames && !rc; k++) {
+            if (moving) {
+                prev_objs = objs;
+                const ptmi_host::Mat t = ptmi_host::multiply(
+                    ptmi_host::translate((double)k * c.move_step[0], (double)k * c.move_step[1], (double)k * c.move_step[2]),
+                    transform0);
+                const ptmi_host::Mat ti = ptmi_host::inverse(t), tit = ptmi_host::transpose(ti);
+                unsigned char* o = objs.data() + (size_t)c.move_object * PTMI_OBJECT_BYTES;
+                std::memcpy(o, t.data(), 128);  // CLObject.transform, inverse, inverseTranspose (ocltracer.go:25-28)
+                std::memcpy(o + 128, ti.data(), 128);
+                std::memcpy(o + 256, tit.data(), 128);
+                if ((rc = ptmi_scene_set_objects(sc, objs.data(), r.n_obj, err, err_len))) break;
+            }
             std::memcpy(cam, cam0, sizeof(cam));
             const ptmi_host::Mat rot = ptmi_host::rotate_y(((double)k * c.orbit_step) * M_PI / 180.0);
             const ptmi_host::Mat inv = ptmi_host::multiply(rot, inv0);
@@ -374,10 +412,15 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             if (c.temporal) {
                 ptmi_reproject_params rp{32, 0, 0.9, 0.02, 0.05};
                 if (c.max_history) rp.max_history = (uint32_t)c.max_history;
-                if ((rc = ptmi_reproject(image, se, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
-                                         k ? prev_cam : nullptr, W, H, &rp, hist[k & 1], acc, acc_se, nullptr, err,
-                                         err_len)))
-                    break;
+                if (moving && k) {
+                    if ((rc = ptmi_motion_table(prev_objs.data(), objs.data(), r.n_obj, motion, nullptr, err, err_len))) break;
+                    rc = ptmi_reproject_motion(image, se, f, hist[(k - 1) & 1], feat[(k - 1) & 1], prev_cam, W, H, &rp,
+                                               hist[k & 1], acc, acc_se, motion, r.n_obj, nullptr, err, err_len);
+                } else {
+                    rc = ptmi_reproject(image, se, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
+                                        k ? prev_cam : nullptr, W, H, &rp, hist[k & 1], acc, acc_se, nullptr, err, err_len);
+                }
+                if (rc) break;
                 frame = acc;
                 frame_se = acc_se;
             }
@@ -395,8 +438,8 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             std::fprintf(stderr, "frame %d (%.6g degrees): wrote %s\n", k, (double)k * c.orbit_step, name.c_str());
         }
     } while (false);
-    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, feat[0], feat[1], hist[0],
-                      hist[1]})
+    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, motion, feat[0], feat[1],
+                      hist[0], hist[1]})
         if (p) (void)hipFree(p);
     ptmi_scene_destroy(sc);
     return rc;
@@ -463,6 +506,11 @@ int main(int argc, char** argv) {
     const std::string png = c.out.empty() ? "out-" + std::to_string(c.samples) + "-" + std::to_string(c.width) +
                                                      "x" + std::to_string(c.height) + ".png"
                                                : c.out;
+    if (c.have_move && (uint32_t)c.move_object >= r.n_obj) {
+        ptmi_host_free_records(&r);
+        ptmi_host_free_textures(&tex);
+        usage("--move-object is outside the scene's objects");
+    }
     if (c.frames > 1) {  // a camera sequence: its frames are written as they finish
         rc = render_frames(c, r, textured ? &tex : nullptr, stream, png, err, sizeof(err));
         ptmi_host_free_records(&r);

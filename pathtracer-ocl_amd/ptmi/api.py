@@ -39,9 +39,11 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_trace_multi_timed", "ptmi_sample_split_point", "ptmi_combine_frames",
            "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate",
            "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts", "ptmi_scene_features",
-           "ptmi_denoise", "ptmi_denoise_work_bytes", "ptmi_scene_set_camera", "ptmi_reproject")
+           "ptmi_denoise", "ptmi_denoise_work_bytes", "ptmi_scene_set_camera", "ptmi_reproject",
+           "ptmi_scene_set_objects", "ptmi_motion_table", "ptmi_reproject_motion")
 FEATURE_DOUBLES = 12    # PTMI_FEATURE_DOUBLES: doubles per pixel of Scene.features
 HISTORY_DOUBLES = 8     # PTMI_HISTORY_DOUBLES: doubles per pixel of a reproject history
+MOTION_DOUBLES = 24     # PTMI_MOTION_DOUBLES: doubles per object of a motion table
 DENOISE_DEMODULATE = 1  # PTMI_DENOISE_DEMODULATE
 
 
@@ -147,6 +149,14 @@ def load_library(path=None):
         lib.ptmi_reproject.restype = i32
         lib.ptmi_reproject.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(ReprojectParams), vp, vp, vp,
                                        vp, cp, sz]
+    if hasattr(lib, "ptmi_reproject_motion"):  # (likewise)
+        lib.ptmi_scene_set_objects.restype = i32
+        lib.ptmi_scene_set_objects.argtypes = [vp, vp, u32, cp, sz]
+        lib.ptmi_motion_table.restype = i32
+        lib.ptmi_motion_table.argtypes = [vp, vp, u32, vp, vp, cp, sz]
+        lib.ptmi_reproject_motion.restype = i32
+        lib.ptmi_reproject_motion.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(ReprojectParams), vp, vp,
+                                              vp, vp, u32, vp, cp, sz]
     if hasattr(lib, "ptmi_diag_scene_tile_cost"):
         lib.ptmi_diag_scene_tile_cost.restype = i32
         lib.ptmi_diag_scene_tile_cost.argtypes = [vp, vp, u32, cp, sz]
@@ -406,6 +416,18 @@ class Scene:
         err = ctypes.create_string_buffer(512)
         _check(self._lib.ptmi_scene_set_camera(self._h, _ptr(cam), err, len(err)), err)
 
+    def set_objects(self, objects):
+        """ptmi_scene_set_objects: new 1024-byte object records, as many as the scene was created with and
+        of the same types (a group keeps its roots and its box).  The scene then renders bit for bit
+        what a scene freshly created with these objects renders; no traversal index is rebuilt.  Blocks
+        until the device's earlier work and the uploads are done."""
+        objs = np.ascontiguousarray(objects)
+        if objs.dtype.itemsize != layout.OBJECT_DTYPE.itemsize:
+            raise TypeError("objects: expected %d-byte records, got %d" % (layout.OBJECT_DTYPE.itemsize,
+                                                                           objs.dtype.itemsize))
+        err = ctypes.create_string_buffer(512)
+        _check(self._lib.ptmi_scene_set_objects(self._h, _ptr(objs), len(objs), err, len(err)), err)
+
     def tile_cost(self):
         """ptmi_diag_scene_tile_cost: the static dispatch class (0..9) of every 8x8 tile as the scene's
         next ordered render sees it, raster order (all 0 without meshes)."""
@@ -592,3 +614,49 @@ def reproject(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_cam
                                          ctypes.c_void_p(out_hist_ptr or None), ctypes.c_void_p(out_rgba_ptr or None),
                                          ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(stream), err, len(err)),
            err)
+
+
+def _object_records(objects, name):
+    objs = np.ascontiguousarray(objects) if objects is not None else None
+    if objs is not None and objs.dtype.itemsize != layout.OBJECT_DTYPE.itemsize:
+        raise TypeError("%s: expected %d-byte records, got %d" % (name, layout.OBJECT_DTYPE.itemsize,
+                                                                  objs.dtype.itemsize))
+    return objs
+
+
+def motion_table(prev_objects, cur_objects, motion_ptr, n_obj=None, stream=0):
+    """ptmi_motion_table: how each object moved between two frames -- from the previous and the current
+    object records (host arrays, the same objects in the same order) into motion_ptr, n_obj *
+    MOTION_DOUBLES doubles of device memory, as reproject_motion takes them.  The arithmetic is
+    ptmi/temporal.py motion_matrices.  Returns when the copy is done."""
+    prev, cur = _object_records(prev_objects, "prev_objects"), _object_records(cur_objects, "cur_objects")
+    if n_obj is None:
+        if prev is None or cur is None or len(prev) != len(cur):
+            raise ValueError("motion_table: two object lists of one length")
+        n_obj = len(cur)
+    err = ctypes.create_string_buffer(256)
+    _check(load_library().ptmi_motion_table(_ptr(prev), _ptr(cur), int(n_obj), ctypes.c_void_p(motion_ptr or None),
+                                            ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def reproject_motion(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_camera, w, h, out_hist_ptr,
+                     motion_ptr, n_obj, out_rgba_ptr=0, out_se_ptr=0, params=None, stream=0):
+    """ptmi_reproject_motion: reproject() for scenes whose objects move -- motion_ptr is the table
+    motion_table() wrote for the previous and the current frame's objects, n_obj its length.  A pixel on
+    a moved object looks its history up where that surface point was; with an all-static table the
+    outputs are reproject()'s bit for bit.  The operation order is ptmi/temporal.py reproject_reference
+    with `motion`."""
+    p = reproject_params(params)
+    cam = None
+    if prev_camera is not None:
+        cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
+        if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
+            raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
+                                                                               cam.dtype.itemsize))
+    err = ctypes.create_string_buffer(512)
+    _check(load_library().ptmi_reproject_motion(
+        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
+        ctypes.c_void_p(prev_hist_ptr or None), ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
+        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_hist_ptr or None),
+        ctypes.c_void_p(out_rgba_ptr or None), ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(motion_ptr or None),
+        int(n_obj), ctypes.c_void_p(stream), err, len(err)), err)

@@ -13,7 +13,11 @@ cameras from one resident scene and accumulates them.
 Limits.  The guides are the pinhole ray through each pixel's centre: depth-of-field blur and sub-pixel
 edges are not in them.  The first hit on glass or a mirror reprojects the glass, not what shows through
 it, and shading that depends on the view (the reflective and refractive materials) lags by the history
-length.  The scene is static: only the camera moves.  The variance needs at least 2 spp per frame (at
+length.  Objects may move between frames (Scene.set_objects, ``move_object``): ``motion_matrices`` and
+the `motion` argument of ``reproject_reference`` restate ptmi_motion_table and ptmi_reproject_motion, which
+carry each first hit back to where that surface point was.  Only what the first-hit records carry is
+followed: shadows, reflections and indirect light that move with an object lag by the history length, and
+geometry inside a mesh does not deform.  The variance needs at least 2 spp per frame (at
 1 spp the standard error is +inf and every pixel resets), and it takes the frames for independent
 estimates: render them with different seeds.  One GPU.
 """
@@ -25,6 +29,9 @@ from . import geom
 
 FEATURE_DOUBLES = 12  # include/ptmi.h PTMI_FEATURE_DOUBLES
 HISTORY_DOUBLES = 8   # PTMI_HISTORY_DOUBLES: colour[3], variance, history length N, 0, 0, 0
+MOTION_DOUBLES = 24   # PTMI_MOTION_DOUBLES: B rows 0-2 [12], G [9], state, 0, 0 per object
+M_STATE = 21
+MOTION_STATIC, MOTION_MOVED, MOTION_NONE = 0.0, 1.0, 2.0
 H_COL, H_VAR, H_N = slice(0, 3), 3, 4
 F_POS, F_T, F_NRM, F_ID = slice(0, 3), 3, slice(4, 7), 7
 DEFAULTS = dict(max_history=32, flags=0, normal_cos=0.9, plane_dist=0.02, min_weight=0.05)
@@ -84,8 +91,45 @@ def _finite4(c, v):
     return np.isfinite(c).all(-1) & np.isfinite(v)
 
 
-def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params=None, details=False):
-    """(hist[W*H*8], out_rgba[W*H*4], out_se[W*H]): the device kernel ptmi_reproject, restated.
+def motion_matrices(prev_objects, cur_objects):
+    """float64[n_obj, MOTION_DOUBLES]: the table ptmi_motion_table writes for the previous and the current
+    object records (the same objects in the same order), restated.  Record k:
+      [0:12]   rows 0-2 of B = prev.transform * cur.inverse, geom.multiply's order: each entry
+               ((a0 b0 + a1 b1) + a2 b2) + a3 b3 -- a current world point -> where that surface point was
+      [12:21]  G = L(prev.inverse_transpose) * L(cur.transform)^T, L the upper-left 3 x 3, row-major, each
+               entry (a0 b0 + a1 b1) + a2 b2 -- the same map for normals (cur.transform^T undoes
+               cur.inverse_transpose)
+      [21]     MOTION_STATIC when the 384 bytes of transform, inverse and inverse_transpose are equal in
+               both records; MOTION_NONE when the bottom row of cur.inverse or of prev.transform is not
+               (0, 0, 0, 1) as values, or an entry of B or G is not finite; else MOTION_MOVED
+      [22:24]  0"""
+    prev, cur = np.ascontiguousarray(prev_objects).reshape(-1), np.ascontiguousarray(cur_objects).reshape(-1)
+    if len(prev) != len(cur):
+        raise ValueError("motion_matrices: %d previous and %d current records" % (len(prev), len(cur)))
+    out = np.zeros((len(cur), MOTION_DOUBLES))
+    with np.errstate(all="ignore"):
+        for k in range(len(cur)):
+            pt, pit = [np.asarray(prev[k][f], dtype=np.float64) for f in ("transform", "inverse_transpose")]
+            ct, ci = [np.asarray(cur[k][f], dtype=np.float64) for f in ("transform", "inverse")]
+            for r in range(3):
+                for c in range(4):
+                    out[k, 4 * r + c] = ((pt[4 * r] * ci[c] + pt[4 * r + 1] * ci[4 + c]) + pt[4 * r + 2] * ci[8 + c]) + \
+                        pt[4 * r + 3] * ci[12 + c]
+                for c in range(3):
+                    out[k, 12 + 3 * r + c] = (pit[4 * r] * ct[4 * c] + pit[4 * r + 1] * ct[4 * c + 1]) + \
+                        pit[4 * r + 2] * ct[4 * c + 2]
+            same = all(np.asarray(prev[k][f]).tobytes() == np.asarray(cur[k][f]).tobytes()
+                       for f in ("transform", "inverse", "inverse_transpose"))
+            affine = all(m[12] == 0.0 and m[13] == 0.0 and m[14] == 0.0 and m[15] == 1.0 for m in (ci, pt))
+            out[k, M_STATE] = MOTION_STATIC if same else \
+                MOTION_MOVED if affine and np.isfinite(out[k, :21]).all() else MOTION_NONE
+    return out
+
+
+def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params=None, details=False,
+                        motion=None, n_obj=0):
+    """(hist[W*H*8], out_rgba[W*H*4], out_se[W*H]): the device kernel ptmi_reproject, restated -- and with
+    `motion` (motion_matrices' table, n_obj records) ptmi_reproject_motion.
 
     Per pixel p with colour c_p = rgba[p][:3], v_p = se_p * se_p and record (x_p, t_p, n_p, id_p):
       RESET  out = (c_p, v_p, N) with N = 1, or N = 0 when c_p or se_p is not finite, when: prev_hist is
@@ -105,6 +149,13 @@ def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h,
       N' = min(h_N + 1, max_history),  a = 1 / N',  b = 1 - a
       c' = h_c + a * (c_p - h_c),  var' = (a * a) * v_p + (b * b) * h_var
     out_hist = (c', var', N', 0, 0, 0);  out_rgba = (c', 1.0);  out_se = sqrt(var').
+
+    With `motion`, for a candidate pixel whose id k = int(id_p) is below n_obj (a NaN id is not), by record
+    k's state: MOTION_STATIC, or k outside the table -- the steps above, unchanged; MOTION_MOVED --
+        x' = B (x_p, 1), each row ((b0 x + b1 y) + b2 z) + b3;   m = G n_p, each row (g0 n.x + g1 n.y) + g2 n.z
+        l = (m0 m0 + m1 m1) + m2 m2;  RESET unless l > 0 and finite;  n' = m / sqrt(l)
+      and x', n' take the places of x_p, n_p in q_k, dn and dd (bound stays plane_dist * t_p); any other
+      state -- RESET.
 
     var' is the variance of the blend when the frames are independent estimates (different seeds).
     details=True also returns a dict of the decisions' test quantities (``undecided``)."""
@@ -127,11 +178,27 @@ def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h,
                 raise ValueError("prev_camera is %dx%d, the frame %dx%d" % (cam["width"], cam["height"], w, h))
             T = cofactor_inverse(cam["inverse"])
             hw, hh, ps = float(cam["half_width"]), float(cam["half_height"]), float(cam["pixel_size"])
+            cand = fin & ~(oid < 0.0)
+            history = np.ones((h, w), dtype=bool)
+            if motion is not None:  # the point and its normal as the previous frame saw them
+                mt = np.asarray(motion, dtype=np.float64).reshape(-1, MOTION_DOUBLES)[:int(n_obj)]
+                known = cand & (oid < float(n_obj))
+                rec = mt[np.where(known, oid, 0.0).astype(np.int64)]
+                moved = known & (rec[..., M_STATE] == MOTION_MOVED)
+                history = ~(known & (rec[..., M_STATE] != MOTION_MOVED) & (rec[..., M_STATE] != MOTION_STATIC))
+                xm = [((rec[..., 4 * k] * x[..., 0] + rec[..., 4 * k + 1] * x[..., 1]) + rec[..., 4 * k + 2] * x[..., 2]) +
+                      rec[..., 4 * k + 3] for k in range(3)]
+                e = [(rec[..., 12 + 3 * k] * n[..., 0] + rec[..., 13 + 3 * k] * n[..., 1]) + rec[..., 14 + 3 * k] * n[..., 2]
+                     for k in range(3)]
+                ln = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]
+                history &= ~(moved & ~((ln > 0.0) & np.isfinite(ln)))
+                root = np.sqrt(ln)
+                x = np.where(moved[..., None], np.stack(xm, -1), x)
+                n = np.where(moved[..., None], np.stack([e[0] / root, e[1] / root, e[2] / root], -1), n)
             q = [((T[4 * k] * x[..., 0] + T[4 * k + 1] * x[..., 1]) + T[4 * k + 2] * x[..., 2]) + T[4 * k + 3]
                  for k in range(3)]
             z = -q[2]
-            cand = fin & ~(oid < 0.0)
-            front = cand & (z > 0.0)
+            front = cand & history & (z > 0.0)
             fu = (hw - q[0] / z) / ps - 0.5
             fv = (hh - q[1] / z) / ps - 0.5
             x0, y0 = np.floor(fu), np.floor(fv)
@@ -214,11 +281,30 @@ def orbit_camera(camera_record, degrees):
     return cam
 
 
+def move_object(objects, index, matrix):
+    """A copy of the object records whose record `index` carries transform' = matrix * transform,
+    inverse' = geom.inverse(transform') and inverse_transpose' = geom.transpose(inverse'): the scene
+    builder's own functions, as a shape's set_transform uses them (the CLI's --move-object gives the same
+    records through the host library)."""
+    out = np.ascontiguousarray(objects).copy()
+    t = geom.multiply([float(a) for a in matrix], [float(a) for a in out[index]["transform"]])
+    inv = geom.inverse(t)
+    out[index]["transform"] = t
+    out[index]["inverse"] = inv
+    out[index]["inverse_transpose"] = geom.transpose(inv)
+    return out
+
+
 def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise=False, reproject_params=None,
-                    denoise_params=None, chunks=0, stream=None):
+                    denoise_params=None, chunks=0, stream=None, objects=None):
     """Render one frame per camera record of `cameras` from the resident `scene` (api.Scene), per frame k:
     set_camera, fill_seeds(seed_stream + k), render_moments, error_map, finalize, features, and with
     `temporal` reproject against frame k - 1, with `denoise` the a-trous filter on the result.
+
+    `objects`: None (the scene's objects stand still), or an iterable of one array of object records per
+    frame.  Frame k then starts with set_objects(objects[k]) before its set_camera, and with `temporal`
+    its history is found through motion_table(objects[k - 1], objects[k]) and reproject_motion, which
+    follows each object's motion.
 
     A generator: yields per frame a dict of float64 torch tensors on the scene's device -- image, se (the
     frame as rendered), feat, out, out_se (what the frame shows: accumulated and / or filtered; image and
@@ -244,10 +330,18 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
                      accumulated=torch.empty(npix * 4, **kw), accumulated_se=torch.empty(npix, **kw),
                      dn=torch.empty(npix * 4, **kw), dn_se=torch.empty(npix, **kw)) for _ in range(2)]
         work = torch.empty(api.denoise_work_bytes(w, h) // 8, **kw) if denoise else None
-    prev, prev_cam = None, None
+        motion = torch.empty(api.MOTION_DOUBLES * 16, **kw) if objects is not None and temporal else None
+    prev, prev_cam, prev_objs, n_obj = None, None, None, 0
+    frame_objects = iter(objects) if objects is not None else None
     for k, cam in enumerate(cameras):
         cur = ring[k & 1]
+        if frame_objects is not None:
+            objs = np.ascontiguousarray(next(frame_objects)).copy()
+            scene.set_objects(objs)  # host-blocking, as set_camera
         scene.set_camera(cam)  # host-blocking: the previous frame's work is done
+        if motion is not None and prev is not None:  # (the device is idle: nothing reads the table)
+            n_obj = len(objs)
+            api.motion_table(prev_objs, objs, motion.data_ptr(), stream=sp)
         with torch.cuda.stream(st):
             api.fill_seeds(seeds.data_ptr(), npix, int(seed_stream) + k, stream=sp)
             scene.render_moments(samples, 0, samples, seeds.data_ptr(), sums.data_ptr(), sq.data_ptr(), chunks=chunks,
@@ -256,11 +350,18 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
             scene.finalize(sums.data_ptr(), cur["image"].data_ptr(), samples, stream=sp)
             scene.features(cur["feat"].data_ptr(), stream=sp)
             frame = dict(image=cur["image"], se=cur["se"], feat=cur["feat"], out=cur["image"], out_se=cur["se"])
-            if temporal:
+            if temporal and motion is not None and prev is not None:
+                api.reproject_motion(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
+                                     prev["hist"].data_ptr(), prev["feat"].data_ptr(), prev_cam, w, h,
+                                     cur["hist"].data_ptr(), motion.data_ptr(), n_obj,
+                                     out_rgba_ptr=cur["accumulated"].data_ptr(),
+                                     out_se_ptr=cur["accumulated_se"].data_ptr(), params=reproject_params, stream=sp)
+            elif temporal:
                 api.reproject(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
                               prev["hist"].data_ptr() if prev else 0, prev["feat"].data_ptr() if prev else 0,
                               prev_cam, w, h, cur["hist"].data_ptr(), out_rgba_ptr=cur["accumulated"].data_ptr(),
                               out_se_ptr=cur["accumulated_se"].data_ptr(), params=reproject_params, stream=sp)
+            if temporal:
                 frame.update(hist=cur["hist"], accumulated=cur["accumulated"], accumulated_se=cur["accumulated_se"],
                              out=cur["accumulated"], out_se=cur["accumulated_se"])
             if denoise:
@@ -269,4 +370,6 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
                             work=work)
                 frame.update(out=cur["dn"], out_se=cur["dn_se"])
         prev, prev_cam = cur, np.asarray(cam).reshape(1).copy()
+        if frame_objects is not None:
+            prev_objs = objs
         yield frame
