@@ -64,7 +64,7 @@ int ptmi_diag_tile_cull_host(const void* objects, uint32_t n_obj, const void* tr
 int ptmi_diag_set_split(ptmi_scene* s, int enable);
 int ptmi_diag_split_passes(const ptmi_scene* s);
 
-/* Work-plan knobs of a resident scene (ptmi_api.cpp ptmi_scene_render); the defaults are
+/* Work-plan knobs of a resident scene (csrc/ptmi_plan.h PlanKnobs, plan_work); the defaults are
  * the product's.  TAIL_TILES: chunked tail tiles of an automatic plan in scenes without
  * meshes (0 = automatic); TAIL_ITEMS / MESH_ITEMS: chunk items per resident wave slot;
  * MIN_CHUNK: fewest samples per chunk item; TILE_ORDER: dispatch order of a mesh scene's
@@ -94,7 +94,7 @@ enum {
 };
 int ptmi_diag_set_knob(ptmi_scene* s, int knob, int value);
 
-/* Kernel feature flags (ptmi_kernels.hip F_*) forced onto every scene created after the
+/* Kernel feature flags (csrc/ptmi_flags.h F_*) forced onto every scene created after the
  * call, process-wide; -1 (the default) lets each scene choose.  Test hook: the generic
  * instantiations must give the specialised ones' images (tests/test_gpu_parity.py). */
 int ptmi_diag_force_flags(int flags);
@@ -112,6 +112,22 @@ int ptmi_diag_scene_flags(const ptmi_scene* s);
 /* Tile ownership a tile-split ptmi_scene_render with this stride uses: 1 diagonal (tile (x, y)
  * to rank (x + y) mod stride), 0 raster (tile t to rank t mod stride); -1 for bad arguments. */
 int ptmi_diag_tile_ownership(const ptmi_scene* s, uint32_t tile_stride);
+
+/* Host only (no device call, no scene): the work plan a render makes of a request (csrc/ptmi_plan.h plan_work).
+ * request[0 .. PTMI_PLAN_REQUEST_WORDS): frame width, height; samples, sample_begin, sample_end; tile_stride,
+ * tile_offset; the caller's chunks (0 automatic); a caller's tile list present (0 / 1), its n_list; the scene's
+ * kernel flags (ptmi_diag_scene_flags' bits: 64 in the statistical RNG mode); resident_waves; second moments asked
+ * for (0 / 1); split_chunk (0: the one-kernel form); then the knobs TAIL_TILES, TAIL_ITEMS, MESH_ITEMS,
+ * MESH_ITEMS_SHARE, MIN_CHUNK, TAIL_SPLIT, TAIL_MIN as the scene holds them (mesh scenes: MIN_CHUNK 64).
+ * plan_out[0 .. PTMI_PLAN_WORDS): n_whole, n_tail, nchunks, chunk_len, n_long, tail_len, s_begin, s_end,
+ * tile_stride, tile_offset (csrc/ptmi_device.h WorkPlan); owned_tiles; the launch's kernel flags; whether the launch
+ * takes the library's diagonal tile list; whether the mesh kernel is the path-pool one; whether the split form
+ * runs; the partial buffer's bytes.  tiles_out[0 .. min(n_tiles, owned_tiles)): the owned tiles' raster indices
+ * (the library's own ownership; untouched for a caller's list).  Returns what the render would: PTMI_ERR_ARG /
+ * PTMI_ERR_UNSUPPORTED with its message for a request it refuses, and PTMI_ERR_ARG for a malformed call. */
+enum { PTMI_PLAN_REQUEST_WORDS = 21, PTMI_PLAN_WORDS = 16 };
+int ptmi_diag_work_plan_host(const uint32_t* request, uint32_t n_request, uint64_t* plan_out, uint32_t n_plan,
+                             uint32_t* tiles_out, uint32_t n_tiles, char* err, size_t err_len);
 
 /* Which form of the a-trous pass ptmi_denoise launches, process-wide: 0 every pass gathers its taps
  * from global memory, 1 the passes at steps 1 and 2 stage the block's pixels and halo in LDS first.

@@ -25,59 +25,41 @@
 #include "ptmi_camcull.h"
 #include "ptmi_device.h"
 #include "ptmi_f16.h"
+#include "ptmi_flags.h"
 #include "ptmi_motion.h"
+#include "ptmi_plan.h"
 
 // DIAGNOSTIC study build (make study): the split execution form, the standalone walk
 // kernels and the measured tile order (ptmi_kernels.hip PTMI_STUDY).  The product has 0.
 #ifndef PTMI_STUDY
 #define PTMI_STUDY 0
 #endif
-
-namespace ptmi {
-hipError_t launch_trace(const DevScene& S, int flags, uint32_t samples, const WorkPlan& WP, const double* seeds,
-                        const double* sunf, double* sums, double* part, uint32_t* item_ctr, double* sq,
-                        hipStream_t st);
-hipError_t launch_sunflower(double* out, uint32_t samples, hipStream_t st);
-hipError_t launch_reduce(const double* part, double* sums, const WorkPlan& WP, int W, int H, bool planes, double* sq,
-                         hipStream_t st);
-hipError_t launch_error_map(const double* sums, const double* sq, uint32_t W, uint32_t H, double* se, double* tile_err,
-                            double* tile_part, double* stats, hipStream_t st);
-hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream_t st);
-hipError_t launch_finalize(const double* sums, double* out, uint32_t npix, uint32_t samples, hipStream_t st);
-hipError_t launch_finalize_counts(const double* sums, double* out, uint32_t npix, hipStream_t st);
-hipError_t launch_select_tiles(const double* tile_err, const uint32_t* in_tiles, uint32_t n_in, double threshold,
-                               uint32_t* out_tiles, uint32_t* count, hipStream_t st);
-hipError_t launch_seeds(double* seeds, uint32_t n, uint64_t stream, hipStream_t st);
-hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st);
-hipError_t launch_camera_terms(const DevScene& S, hipStream_t st);
-hipError_t launch_hemi_table(double* out, int* mismatch, hipStream_t st);
-hipError_t launch_combine(const double* parts, uint32_t nparts, size_t npix, double* out, uint32_t samples,
-                          hipStream_t st);
-hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st);
-hipError_t launch_denoise(const double* rgba, const double* se, const double* feat, uint32_t W, uint32_t H,
-                          uint32_t iterations, bool demod, double sigma_l, double sigma_d, uint32_t npow, double* out,
-                          double* out_se, double* work, int variant, hipStream_t st);
-hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
-                            const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
-                            double* out_se, const double* motion, int32_t n_obj, hipStream_t st);
-const void* trace_kernel_symbol(int flags);
-bool tile_list_supported(int flags);
-int trace_kernel_flags(int flags);
-#if PTMI_STUDY
-hipError_t launch_tile_order(unsigned long long* cost, uint32_t n_whole, uint32_t n_tail, uint32_t stride,
-                             uint32_t offset, uint32_t* order, hipStream_t st);
-bool split_supported(int flags);
-const void* trace_split_symbol(int flags);
-const void* walk_split_symbol();
-hipError_t launch_split_pass(const DevScene& S, int flags, uint32_t samples, const WorkPlan& WP, const SplitBufs& B,
-                             const double* seeds, const double* sunf, double* part, uint32_t walk_grid,
-                             hipStream_t st);
-#endif
-int trace_block_threads(int flags);
-int trace_tiles_per_block(int flags);
-}  // namespace ptmi
+#include "ptmi_launch.h"
 
 using namespace ptmi;
+
+static_assert(kPlanOk == PTMI_OK && kPlanErrArg == PTMI_ERR_ARG && kPlanErrUnsupported == PTMI_ERR_UNSUPPORTED,
+              "ptmi_plan.h states the status codes of include/ptmi.h");
+
+// A device allocation that a scene owns and that only grows: pointer plus capacity in bytes.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    // Room for `bytes`: nothing if it is there; else, after the stream's work on the old allocation, a new one
+    // (contents are not kept).
+    hipError_t reserve(size_t bytes, hipStream_t st) {
+        if (bytes <= cap) return hipSuccess;
+        hipError_t e = hipSuccess;
+        if (p && (e = hipStreamSynchronize(st)) == hipSuccess && (e = hipFree(p)) == hipSuccess) p = nullptr, cap = 0;
+        if (e == hipSuccess && (e = hipMalloc((void**)&p, bytes)) == hipSuccess) cap = bytes;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+};
 
 // What mesh_tile_cost needs of a scene, kept with it so the tile classes are computed on
 // the first render that orders tiles, and only for the tiles that render owns: the camera
@@ -91,7 +73,7 @@ struct TileCostInput {
     std::vector<Obj> objs;
 };
 
-// The kernel flags of a scene (ptmi_kernels.hip F_*) in two parts: what the objects, the triangles, the
+// The kernel flags of a scene (ptmi_flags.h F_*) in two parts: what the objects, the triangles, the
 // traversal index and the force hook decide (SceneFlagBasis, fixed when the scene is created), and what the
 // camera adds (scene_flags), so that a camera change re-derives the instantiation from the same code.
 struct SceneFlagBasis {
@@ -107,20 +89,13 @@ struct ptmi_scene {
     int device = 0;
     DevScene dev{};
     void* buffers[15] = {};  // [10..12]: texture arrays, [13]: hemisphere table, [14]: camera record
-    double* partial = nullptr;  // chunk partial sums, grown on demand
+    DevBuf<double> partial;     // chunk partial sums, grown on demand
     double* sunf = nullptr;     // DoF aperture table for sunf_samples (sunflower_kernel)
     uint32_t sunf_samples = 0;
-    size_t partial_bytes = 0;
     int resident_waves = 0;  // device-wide resident waves of trace_kernel
-    uint32_t tail_tiles = 0;  // chunked tiles at the end of an automatic launch; 0: default (see render)
-    uint32_t tail_items = 6;  // chunk items per resident wave slot in the tail (scenes without meshes; see render)
-    uint32_t mesh_items = 32;  // chunk items per resident wave slot, mesh scenes (every tile chunked)
-    uint32_t mesh_items_share = 48;  // ... in a sample-split rank's share (a sub-range of the samples)
-    uint32_t min_chunk = 32;   // fewest samples per chunk item (see render)
-    uint32_t tail_split = 4;   // mesh scenes: the last chunk round cut into this many (see render)
-    uint32_t tail_min = 0;     // ... while those keep at least this many samples; 0: automatic (see render)
+    PlanKnobs knobs;         // of the work plan (ptmi_plan.h; ptmi_diag_set_knob)
     // Mesh scenes: per-tile cost class (mesh_tile_cost) and the dispatch order built from it
-    // for the last (tile_stride, tile_offset) rendered (see render).
+    // for the last (tile_stride, tile_offset) rendered (see ensure_dispatch_order).
     // 0: raster order, 1: static (hull-hit classes), 2: measured by the last launch (needs a
     // build with PTMI_TILE_COST=1 -- see ptmi_kernels.hip item_cost_add; else the order is
     // arbitrary within the static plan, which never changes a result)
@@ -128,18 +103,24 @@ struct ptmi_scene {
     TileCostInput tc_in;              // mesh scenes: the inputs of the tile classes
     std::vector<uint8_t> tile_cost;   // per tile: its class, or kCostUnset until a render needs it
     std::vector<uint32_t> order_host;
-    uint32_t* order_dev = nullptr;
+    DevBuf<uint32_t> order_dev;
     unsigned long long* cost_dev = nullptr;  // study build: per-tile durations of the launches since the last order
-    uint32_t order_stride = 0, order_offset = 0, order_n = 0, order_whole = 0, order_cap = 0;
-    // Tile-split launches of the affine mesh kernels: the owned-tile list (WorkPlan::tiles)
-    // of the last (tile_stride, tile_offset) rendered with one (see owned_tile).
-    std::vector<uint32_t> tlist_host;
-    uint32_t* tlist_dev = nullptr;
-    uint32_t* item_ctr = nullptr;  // the mesh kernels' work-item counter (ptmi_kernels.hip take_item), zeroed per launch
-    uint32_t tlist_stride = 0, tlist_offset = 0, tlist_cap = 0;
+    uint32_t order_stride = 0, order_offset = 0, order_n = 0, order_whole = 0;
     bool order_tlist = false;  // the dispatch order was built for a list launch
+    void drop_dispatch_order() { order_n = 0; }  // the next ordered render builds it again
+    void drop_tile_classes() {  // the view or the group objects changed: new classes, and the order built from them
+        tile_cost.clear();
+        drop_dispatch_order();
+    }
+    // Tile-split launches of the affine mesh kernels: the owned-tile list (WorkPlan::tiles)
+    // of the last (tile_stride, tile_offset) rendered with one (see ensure_tile_list).
+    std::vector<uint32_t> tlist_host;
+    DevBuf<uint32_t> tlist_dev;
+    uint32_t* item_ctr = nullptr;  // the mesh kernels' work-item counter (ptmi_kernels.hip take_item), zeroed per launch
+    uint32_t tlist_stride = 0, tlist_offset = 0;
     uint32_t width = 0, height = 0;
-    int flags = 0;  // scene features -> kernel instantiation (ptmi_kernels.hip F_*)
+    int flags = 0;  // scene features -> kernel instantiation (ptmi_flags.h F_*)
+    int launch_flags() const { return with_rng(flags, rng == PTMI_RNG_XOSHIRO); }  // ... with the RNG mode's bit
     SceneFlagBasis basis;  // what `flags` takes from everything but the camera (ptmi_scene_set_camera)
     // ptmi_scene_set_objects: the converted list as uploaded (type runs, each group's RootRec slot in
     // child_base), the caller's records' identity fields, and the sizes of the two allocations that follow
@@ -167,6 +148,9 @@ struct ptmi_scene {
     size_t split_bytes = 0;
     uint32_t* split_host = nullptr;  // pinned: the request count read back at a check
     uint32_t split_passes = 0;       // passes of the last split render (diagnostics)
+    uint32_t plan_split_chunk() const { return split ? split_chunk : 0; }  // PlanRequest::split_chunk
+#else
+    uint32_t plan_split_chunk() const { return 0; }  // the one-kernel form is the only one here
 #endif
 };
 
@@ -423,13 +407,13 @@ bool camera_affine(const DevCamera& cam) {
 
 int scene_flags(const SceneFlagBasis& fb, const DevCamera& cam) {
     int flags = fb.obj_bits;
-    if (cam.aperture != 0) flags |= 8;                                  // F_DOF
+    if (cam.aperture != 0) flags |= F_DOF;
     // Affine scene: every inverse ends in (+-0, +-0, +-0, 1), inverse transposes have +-0 in
     // column 3 of rows 0-2, triangle normals have a finite w.  Otherwise F_PROJ: the generic
     // instantiation with the w lanes.
-    if (!(fb.affine && camera_affine(cam))) flags |= 16;                // F_PROJ
-    if (fb.textured) flags = 63;
-    if (fb.forced >= 0) flags = fb.forced & 63;
+    if (!(fb.affine && camera_affine(cam))) flags |= F_PROJ;
+    if (fb.textured) flags = F_GENERIC;
+    if (fb.forced >= 0) flags = fb.forced & F_GENERIC;
     return flags | fb.wide;  // (never a 16-bit stack for 31-bit codes: F_PROJ and F_TEX kernels have 32-bit ones)
 }
 
@@ -461,9 +445,9 @@ void object_flag_basis(const std::vector<DevObject>& objs, bool tris_affine, Sce
     fb.affine = true;
     fb.textured = false;
     for (const DevObject& o : objs) {
-        if (o.type == 4) fb.obj_bits |= 1;                                    // F_GROUPS
-        if (o.type == 2 || o.type == 3) fb.obj_bits |= 2;                     // F_CYLCUBE
-        if (o.reflectivity != 0.0 || o.refractive_index != 1.0) fb.obj_bits |= 4;  // F_MATERIALS
+        if (o.type == 4) fb.obj_bits |= F_GROUPS;
+        if (o.type == 2 || o.type == 3) fb.obj_bits |= F_CYLCUBE;
+        if (o.reflectivity != 0.0 || o.refractive_index != 1.0) fb.obj_bits |= F_MATERIALS;
     }
     for (const DevObject& o : objs)
         fb.affine = fb.affine && o.inv[12] == 0.0 && o.inv[13] == 0.0 && o.inv[14] == 0.0 && o.inv[15] == 1.0 &&
@@ -538,7 +522,7 @@ int prepare_scene(const void* objects, uint32_t n_obj, const void* triangles, ui
     // Child codes past 16 bits (>= 2^15 Node4s or triangles): a traversal stack of 32-bit
     // entries -- the affine F_WIDE instantiation (ptmi_kernels.hip trace_groups), or the
     // generic one for non-affine scenes (round 5 sent every such scene to the generic one).
-    fb.wide = hs.leaf_bit != kLeafNarrow ? 256 : 0;                           // F_WIDE
+    fb.wide = hs.leaf_bit != kLeafNarrow ? F_WIDE : 0;
     fb.forced = g_force_flags.load();  // ptmi_diag_force_flags (tests): one load
     const int flags = scene_flags(fb, hs.cam);
     if (textures) {
@@ -571,7 +555,7 @@ hipError_t resident_waves(ptmi_scene* s) {
     hipDeviceProp_t p;
     hipError_t e = hipGetDeviceProperties(&p, s->device);
     if (e != hipSuccess) return e;
-    const int flags = s->flags | (s->rng == PTMI_RNG_XOSHIRO ? 64 : 0);  // F_XRNG
+    const int flags = s->launch_flags();
     s->resident_waves = p.multiProcessorCount * 16;
     int blocks_per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, trace_kernel_symbol(flags),
@@ -596,7 +580,7 @@ constexpr uint8_t kCostUnset = 0xFF;
 // (gopher: 9.8 Node4 visits and 5.3 triangle tests per walk against the teapot's 6.7 and 2.3), so
 // a walk phase is worth more parked lanes.  Scenes without meshes never walk.
 static int32_t walk_batch_for(const HostScene& hs) {
-    if (!(hs.flags & 1)) return 64;
+    if (!(hs.flags & F_GROUPS)) return 64;
     return hs.n_tri >= 12000 ? 32 : 28;
 }
 
@@ -786,8 +770,8 @@ int upload_scene(const HostScene& hs, int device_index, const ptmi_textures* tex
     // share): the C4 8-rank shares (256 samples) take 81.3 ms on average with 4 chunks of 64
     // against 85.4 ms with 7 of 37 (the items' start-up and end-of-item idle lanes), 93.5 ms
     // with 2 of 128 (a coarser drain); the C5 tile-split shares are flat (profiles/r4/shards).
-    if (hs.flags & 1) s->min_chunk = 64;
-    if (hs.flags & 1) s->tc_in = tile_cost_input(hs);  // tile classes: on the first ordered render
+    if (hs.flags & F_GROUPS) s->knobs.min_chunk = 64;
+    if (hs.flags & F_GROUPS) s->tc_in = tile_cost_input(hs);  // tile classes: on the first ordered render
     s->dev.n_tri = hs.n_tri;
     s->dev.cam = hs.cam;
     {  // the camera record in device memory (ptmi_kernels.hip camera_ptr)
@@ -872,7 +856,7 @@ int render_split(ptmi_scene* s, uint32_t samples, const WorkPlan& wp, const doub
     for (;;) {
         HIP_TRY(hipMemsetAsync(B.cnt, 0, 4, st));  // this pass's request count
         HIP_TRY(hipMemsetAsync(B.cnt + 2, 0, 4, st));  // and yield count
-        HIP_TRY(launch_split_pass(s->dev, flags, samples, wp, B, seeds, s->sunf, s->partial, walk_grid, st));
+        HIP_TRY(launch_split_pass(s->dev, flags, samples, wp, B, seeds, s->sunf, s->partial.p, walk_grid, st));
         pass++;
         if (pass % s->split_sync == 0) {
             HIP_TRY(hipMemcpyAsync(s->split_host, B.cnt, 12, hipMemcpyDeviceToHost, st));
@@ -989,14 +973,14 @@ void ptmi_scene_destroy(ptmi_scene* s) {
     (void)hipSetDevice(s->device);
     for (void* b : s->buffers)
         if (b) (void)hipFree(b);
-    if (s->partial) (void)hipFree(s->partial);
+    s->partial.release();
+    s->order_dev.release();
+    s->tlist_dev.release();
     if (s->sunf) (void)hipFree(s->sunf);
 #if PTMI_STUDY
     if (s->split_mem) (void)hipFree(s->split_mem);
     if (s->split_host) (void)hipHostFree(s->split_host);
 #endif
-    if (s->order_dev) (void)hipFree(s->order_dev);
-    if (s->tlist_dev) (void)hipFree(s->tlist_dev);
     if (s->item_ctr) (void)hipFree(s->item_ctr);
     if (s->cost_dev) (void)hipFree(s->cost_dev);
     for (auto& e : s->events) {
@@ -1014,20 +998,101 @@ int ptmi_scene_size(const ptmi_scene* s, uint32_t* w, uint32_t* h) {
     return PTMI_OK;
 }
 
-// Tile ownership of a tile-split render (ptmi_scene_render): diagonal for affine narrow-code
-// mesh scenes in parity mode whose tile rows divide by the stride (the F_TLIST instantiations),
-// raster striding otherwise.  Exported as ptmi_diag_tile_ownership, so callers that mask shards
-// use the library's own decision (ptmi/dist.py had restated it).
-static bool diagonal_tiles(const ptmi_scene* s, uint32_t tile_stride) {
-    const int kflags0 = s->flags | (s->rng == PTMI_RNG_XOSHIRO ? 64 : 0);
-    const uint32_t tiles_x = (s->width + kTile - 1) / kTile;
-#if PTMI_STUDY
-    if (s->split) return false;
-#endif
-    return tile_stride > 1 && tile_list_supported(kflags0) && tiles_x % tile_stride == 0;
+}  // extern "C"
+
+// The steps of render_frame that keep a resource of the scene in step with the plan (ptmi_plan.h).
+
+// The diagonal owned-tile list (WorkPlan::tiles) of a tile-split launch that takes one.
+static int ensure_tile_list(ptmi_scene* s, PlanResult& plan, hipStream_t st, char* err, size_t err_len) {
+    const TileOwnership& own = plan.own;
+    if (!own.tlist) return PTMI_OK;
+    const uint32_t n = plan.owned_tiles;
+    if (s->tlist_stride != own.stride || s->tlist_offset != own.offset || s->tlist_host.size() != n) {
+        HIP_TRY(hipStreamSynchronize(st));  // tlist_host may still feed an earlier copy
+        s->tlist_host.resize(n);
+        for (uint32_t k = 0; k < n; k++) s->tlist_host[k] = own(k);
+        HIP_TRY(s->tlist_dev.reserve((size_t)n * sizeof(uint32_t), st));
+        HIP_TRY(hipMemcpyAsync(s->tlist_dev.p, s->tlist_host.data(), (size_t)n * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, st));
+        s->tlist_stride = own.stride;
+        s->tlist_offset = own.offset;
+        s->drop_dispatch_order();  // it indexes owned tiles
+    }
+    plan.wp.tiles = s->tlist_dev.p;
+    return PTMI_OK;
 }
 
-}  // extern "C"
+// Mesh scenes: the dispatch order of the work items (WorkPlan::order) -- whole tiles among themselves,
+// then each chunk round's tiles among themselves (which tiles are whole and which
+// chunked stays the raster-defined plan, so no pixel's sums change).  A rank's
+// first launch (or one after its tile ownership or plan changed) takes the static
+// order (mesh_tile_cost's hull-hit classes, costliest first, raster order within a
+// class); with tile_order 2 every launch also measures its items and
+// tile_order_kernel writes the next launch's order from those durations.  (The
+// kernels without meshes do not measure: see item_cost_add.)
+static int ensure_dispatch_order(ptmi_scene* s, PlanResult& plan, hipStream_t st, char* err, size_t err_len) {
+    const TileOwnership& own = plan.own;
+    WorkPlan& wp = plan.wp;
+    const uint32_t n = plan.owned_tiles;
+    if (plan.split || !s->tile_order || n == 0 || !(s->flags & F_GROUPS)) return PTMI_OK;
+#if PTMI_STUDY
+    if (s->tile_order == 2 && !s->cost_dev) {
+        HIP_TRY(hipMalloc((void**)&s->cost_dev, (size_t)own.tiles * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(s->cost_dev, 0, (size_t)own.tiles * sizeof(unsigned long long), st));
+    }
+#endif
+    if (s->order_stride != own.stride || s->order_offset != own.offset || s->order_n != n ||
+        s->order_tlist != own.tlist || s->order_whole != wp.n_whole) {
+        HIP_TRY(hipStreamSynchronize(st));  // order_host may still feed an earlier copy
+        mesh_tile_cost(s->tc_in, s->tile_cost, n, own);  // this render's tiles, once
+        s->order_host.resize(n);
+        for (uint32_t k = 0; k < wp.n_whole; k++) s->order_host[k] = k;
+        for (uint32_t k = 0; k < wp.n_tail; k++) s->order_host[wp.n_whole + k] = k;
+        std::stable_sort(s->order_host.begin() + wp.n_whole, s->order_host.end(), [&](uint32_t a, uint32_t b) {
+            return s->tile_cost[own(wp.n_whole + a)] > s->tile_cost[own(wp.n_whole + b)];
+        });
+        HIP_TRY(s->order_dev.reserve((size_t)n * sizeof(uint32_t), st));
+        HIP_TRY(hipMemcpyAsync(s->order_dev.p, s->order_host.data(), (size_t)n * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, st));
+        s->order_stride = own.stride;
+        s->order_offset = own.offset;
+        s->order_n = n;
+        s->order_tlist = own.tlist;
+        s->order_whole = wp.n_whole;
+    }
+    wp.order = s->order_dev.p;
+#if PTMI_STUDY
+    wp.cost = s->tile_order == 2 ? s->cost_dev : nullptr;
+#endif
+    return PTMI_OK;
+}
+
+// The DoF aperture table of a frame of `samples` samples (sunflower_kernel).
+static int ensure_dof_table(ptmi_scene* s, uint32_t samples, hipStream_t st, char* err, size_t err_len) {
+    if (!(s->flags & F_DOF) || s->dev.cam.aperture == 0 || s->sunf_samples == samples) return PTMI_OK;
+    if (s->sunf) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipFree(s->sunf));
+        s->sunf = nullptr;
+    }
+    HIP_TRY(hipMalloc((void**)&s->sunf, (size_t)samples * 2 * sizeof(double)));
+    HIP_TRY(launch_sunflower(s->sunf, samples, st));
+    s->sunf_samples = samples;
+    return PTMI_OK;
+}
+
+// A (start, stop) event pair for a timed launch, from the scene's spares.
+static int take_events(ptmi_scene* s, hipEvent_t& ev0, hipEvent_t& ev1, char* err, size_t err_len) {
+    for (hipEvent_t* e : {&ev0, &ev1}) {
+        if (!s->spare.empty()) {
+            *e = s->spare.back();
+            s->spare.pop_back();
+        } else {
+            HIP_TRY(hipEventCreate(e));
+        }
+    }
+    return PTMI_OK;
+}
 
 // ptmi_scene_render (sq_dev == nullptr) and ptmi_scene_render_moments (sq_dev: W*H second moments):
 // one plan for both, so the moment render's colour sums are the plain render's bit for bit.
@@ -1037,277 +1102,50 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
                         uint32_t tile_stride, uint32_t tile_offset, const double* seeds_dev, double* sums_dev,
                         double* sq_dev, uint32_t chunks, void* hip_stream, char* err, size_t err_len,
                         const uint32_t* list_dev = nullptr, uint32_t n_list = 0) {
-    if (!s || !seeds_dev || !sums_dev || samples == 0 || sample_begin > sample_end || sample_end > samples ||
-        tile_stride == 0 || tile_offset >= tile_stride) {
-        set_err(err, err_len, "bad render arguments (samples %u range [%u,%u) tiles %u/%u)", samples, sample_begin,
-                sample_end, tile_offset, tile_stride);
-        return PTMI_ERR_ARG;
-    }
+    PlanRequest rq;
+    rq.samples = samples, rq.sample_begin = sample_begin, rq.sample_end = sample_end;
+    rq.tile_stride = tile_stride, rq.tile_offset = tile_offset;
+    if (!s || !seeds_dev || !sums_dev) return plan_bad_arguments(rq, err, err_len);
+    rq.width = s->width, rq.height = s->height;
+    rq.chunks = chunks;
+    rq.has_list = list_dev != nullptr, rq.n_list = n_list;
+    rq.flags = s->launch_flags();
+    rq.resident_waves = s->resident_waves;
+    rq.moments = sq_dev != nullptr;
+    rq.split_chunk = s->plan_split_chunk();
+    PlanResult plan;
+    int rc = plan_work(rq, s->knobs, plan, err, err_len);
+    if (rc) return rc;
+    const WorkPlan& wp = plan.wp;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    const uint32_t W = s->width, H = s->height, npix = W * H;
-    const uint32_t range = sample_end - sample_begin;
-    const uint32_t tiles_x = (W + kTile - 1) / kTile, tiles = tiles_x * ((H + kTile - 1) / kTile);
-    const int kflags0 = s->flags | (s->rng == PTMI_RNG_XOSHIRO ? 64 : 0);
-    // Tile ownership of a tile-split launch.  Raster: tiles offset, offset + stride, ...; with
-    // 160 tiles per row (1280 px) and stride 8 that gives every rank the same tile columns in
-    // every row -- vertical stripes, which split a mesh unevenly (C5 8 ranks: max/mean 1.05).
-    // Affine mesh scenes whose tile rows divide by the stride take the diagonal instead --
-    // tile (x, y) belongs to rank (x + y) mod stride, each row holding tiles_x / stride of a
-    // rank's tiles -- through the F_TLIST instantiations (WorkPlan::tiles), so the one-GPU
-    // kernels are untouched (profiles/r5/tile_skew).  Every pixel's sums are the same either way.
-    const bool tlist = !list_dev && diagonal_tiles(s, tile_stride);
-    const uint32_t per_row = tiles_x / tile_stride;
-    auto owned_tile = [&](uint32_t k) -> uint32_t {
-        if (!tlist) return tile_offset + k * tile_stride;
-        const uint32_t ty = k / per_row, j = k - ty * per_row;
-        return ty * tiles_x + (tile_offset + tile_stride - ty % tile_stride) % tile_stride + j * tile_stride;
-    };
-    const uint32_t owned_tiles = list_dev ? n_list
-                                 : tlist  ? tiles / tile_stride
-                                          : (tiles + tile_stride - 1 - tile_offset) / tile_stride;
-    // Work items (WorkPlan, ptmi_device.h).  Automatic (chunks == 0), scenes without
-    // meshes: whole tiles first, then the last ~0.5 resident waves' worth of tiles
-    // split into sample chunks, so that short items fill the end of the launch (~6 per
-    // resident wave slot, >= 32 samples each).  A whole-tile item pays its start-up
-    // and the spread of its lanes' path lengths once for the whole range, and sums in
-    // sample order without a partial buffer.  C2 (2048 spp, 4096 resident waves): 185.3 ms
-    // with every tile chunked; 181.6 / 178.2 / 177.5 / 176.8 / 182.5 ms with 9000 / 4096 /
-    // 3072 / 2048 / 1024 chunked tail tiles.
-    // Round 3: ~6 items per slot, with the partials as r, g, b planes (24 B per lane and
-    // item): C2 2048 spp 154.0 / 154.5 / 154.9 / 155.3 ms and 0.164 / 0.143 / 0.131 / 0.12 GB
-    // of HBM traffic per launch at 8 / 6 / 5 / 4 items (profiles/r3/tail_items).
-    // Mesh scenes chunk every tile (~32 items per slot): a tile's cost there depends on
-    // how much mesh it sees, so whole tiles leave a long tail (C4 801 -> 1008 ms).
-    // An explicit chunk count splits every tile.
-    WorkPlan wp{};
-    wp.s_begin = sample_begin;
-    wp.s_end = sample_end;
-    wp.tile_stride = tile_stride;
-    wp.tile_offset = tile_offset;
-    // Affine mesh scenes in parity mode, when the split form is selected (render_split): pixel-chunks of
-    // split_chunk samples (an explicit `chunks` sets the chunk count as for the one-kernel
-    // form, so both forms then sum the same chunks in the same order).
-    // (a caller's list: the F_TLIST instantiations where the scene's family has them, else the moment
-    // instantiation's own select on WorkPlan::tiles, ptmi_kernels.hip kTilesOf)
-    const int kflags = kflags0 | ((tlist || (list_dev && tile_list_supported(kflags0))) ? 128 : 0);  // F_TLIST
-#if PTMI_STUDY
-    const bool split = s->split && split_supported(kflags) && range > 0;
-#else
-    constexpr bool split = false;
-#endif
-#if PTMI_STUDY
-    if (split) {
-        uint32_t nch = chunks ? chunks : (range + s->split_chunk - 1) / s->split_chunk;
-        nch = std::max<uint32_t>(1, std::min<uint32_t>(nch, range));
-        wp.chunk_len = (range + nch - 1) / nch;
-        wp.nchunks = (range + wp.chunk_len - 1) / wp.chunk_len;
-        wp.n_long = wp.nchunks;
-        wp.tail_len = wp.chunk_len;
-        wp.n_whole = 0;
-        wp.n_tail = owned_tiles;
-    }
-#endif
-    uint32_t n_tail = owned_tiles;
-    const bool auto_chunks = chunks == 0;
-    if (split) {
-        chunks = wp.nchunks;
-    } else if (chunks == 0) {
-        const bool mesh = (s->flags & 1) != 0;  // F_GROUPS
-        if (!mesh || s->tail_tiles)
-            n_tail = std::min<uint32_t>(owned_tiles, s->tail_tiles ? s->tail_tiles : (uint32_t)(s->resident_waves / 2));
-        // A sample-split rank of a mesh scene holding at most a quarter of the samples (every tile):
-        // 48 items per slot instead of 32 (round 6, C4 8 ranks: projected efficiency 0.896 -> 0.904;
-        // at 2 ranks 48 cost 0.962 -> 0.940, and the one-GPU frame 1.7 %, so those keep 32).
-        // Tile-split ranks keep 32 (C5: 0.857 / 0.854).
-        const bool sample_share = mesh && tile_stride == 1 && (uint64_t)range * 4 <= samples;
-        const uint64_t want =
-            (uint64_t)s->resident_waves * (mesh ? (sample_share ? s->mesh_items_share : s->mesh_items) : s->tail_items);
-        // A mesh scene's tile-split rank owns 1/N of the tiles, so a chunk round is a fraction
-        // of the machine (2,400 items at N = 8 against 4,096 wave slots) and the 64-sample floor
-        // held it at ~19 items per slot; half the floor lets the items-per-slot target bind
-        // (C5 8 ranks: 55 chunks of 38 samples, projected efficiency 0.81 -> 0.84; C4 tile split
-        // 0.80 -> 0.81).  Sample-split ranks keep every tile and the floor (C4 0.90 -> 0.86 at
-        // the half floor; profiles/r5/shards/chunks).
-        const uint32_t floor = (mesh && tile_stride > 1) ? std::max<uint32_t>(1, s->min_chunk / 2) : s->min_chunk;
-        chunks = (uint32_t)std::min<uint64_t>((want + n_tail - 1) / std::max<uint32_t>(n_tail, 1),
-                                              std::max<uint32_t>(range / floor, 1));
-    }
-    // The path pool of the tile-list kernels numbers an item's paths 64 x its samples in 32 bits.
-    if (kflags & 128) chunks = std::max<uint32_t>(chunks, (range + (1u << 25) - 1) >> 25);
-    chunks = std::max<uint32_t>(1, std::min<uint32_t>(chunks, std::max<uint32_t>(range, 1)));
-    const uint32_t chunk_len = range == 0 ? 1 : (range + chunks - 1) / chunks;
-    chunks = range == 0 ? 1 : (range + chunk_len - 1) / chunk_len;
-    if (chunks == 1 && !split) n_tail = 0;  // one chunk: every tile is whole
-    wp.n_whole = owned_tiles - n_tail;
-    wp.n_tail = n_tail;
-    wp.nchunks = chunks;
-    wp.chunk_len = chunk_len;
-    wp.n_long = chunks;
-    wp.tail_len = chunk_len;
-    // Mesh scenes, automatic plans: the last chunk round is cut into tail_split shorter rounds,
-    // numbered last (and so dispatched last), so the launch drains on short items -- the
-    // end-of-launch ramp was 3.1 % of the one-GPU C5 frame's slot-time (profiles/r4/timeline).
-    // 2048 spp, one MI355X (profiles/r5/tail_split): C5 876 -> 865 ms, C4 unchanged.  Only
-    // while the short chunks keep >= min_chunk / 2 samples: on 8-rank shares (64-sample chunks)
-    // 16-sample ones cost C4's sample split more at each item's end than they saved at the
-    // launch's (projected efficiency 0.893 -> 0.878) and left C5's tile split as it was.
-    // Round 6: the path-pool kernels (affine mesh scenes in parity mode) have no per-item lane
-    // drain, so their short chunks may go down to 8 samples (tail_min): an 8-rank C5 tile share
-    // (38-sample chunks) drained 9.8 ms of its 108.9 ms on its last round's costliest tiles
-    // (profiles/r6/timeline).  Chunks are summed in chunk order either way.
-    const bool pooled = (kflags0 & 1) && !(kflags0 & (16 | 32 | 64));  // F_GROUPS, not F_PROJ / F_TEX / F_XRNG
-    const uint32_t tail_min = s->tail_min ? s->tail_min : pooled ? 8u : s->min_chunk / 2;
-    const uint32_t tl = (chunk_len + std::max<uint32_t>(s->tail_split, 1) - 1) / std::max<uint32_t>(s->tail_split, 1);
-    if (!split && auto_chunks && (s->flags & 1) && chunks > 1 && s->tail_split > 1 && tl >= tail_min) {
-        const uint32_t rest = range - (chunks - 1) * chunk_len;
-        wp.n_long = chunks - 1;
-        wp.tail_len = tl;
-        wp.nchunks = wp.n_long + (rest + tl - 1) / tl;
-        chunks = wp.nchunks;
-    }
-    wp.order = nullptr;
-    wp.cost = nullptr;
-    wp.tiles = nullptr;
-    if (tlist) {
-        if (s->tlist_stride != tile_stride || s->tlist_offset != tile_offset || s->tlist_host.size() != owned_tiles) {
-            HIP_TRY(hipStreamSynchronize(st));  // tlist_host may still feed an earlier copy
-            s->tlist_host.resize(owned_tiles);
-            for (uint32_t k = 0; k < owned_tiles; k++) s->tlist_host[k] = owned_tile(k);
-            if (s->tlist_dev && s->tlist_cap < owned_tiles) {
-                HIP_TRY(hipFree(s->tlist_dev));
-                s->tlist_dev = nullptr;
-            }
-            if (!s->tlist_dev) {
-                HIP_TRY(hipMalloc((void**)&s->tlist_dev, (size_t)owned_tiles * sizeof(uint32_t)));
-                s->tlist_cap = owned_tiles;
-            }
-            HIP_TRY(hipMemcpyAsync(s->tlist_dev, s->tlist_host.data(), (size_t)owned_tiles * sizeof(uint32_t),
-                                   hipMemcpyHostToDevice, st));
-            s->tlist_stride = tile_stride;
-            s->tlist_offset = tile_offset;
-            s->order_n = 0;  // the dispatch order indexes owned tiles: rebuild it
-        }
-        wp.tiles = s->tlist_dev;
-    }
+    if ((rc = ensure_tile_list(s, plan, st, err, err_len))) return rc;
     // A caller's list lives on the device: the library's cached diagonal list and its cached
     // dispatch order (both built on the host from its own ownership) are left alone, and the items
     // run in list order.  (A costliest-first order of listed tiles would need the list on the host.)
-    if (list_dev) wp.tiles = list_dev;
-    if (sq_dev) {
-#if PTMI_STUDY
-        if (split) {
-            set_err(err, err_len, "the split execution form has no moment variant");
-            return PTMI_ERR_UNSUPPORTED;
-        }
-#endif
-        // The path pool numbers an item's paths 64 x its samples in 32 bits (trace_groups_pool's
-        // `total`): with or without a tile list, an item of 2^26 samples or more would wrap.
-        if (pooled && (uint64_t)std::max(wp.chunk_len, wp.tail_len) >= (1ull << 26) && range > 0) {
-            set_err(err, err_len, "moment render: a pooled work item of %u samples (>= 2^26); use more chunks",
-                    std::max(wp.chunk_len, wp.tail_len));
-            return PTMI_ERR_ARG;
-        }
-    }
-    const bool mesh_plan = (s->flags & 1) != 0;  // F_GROUPS
-    if (!split && s->tile_order && owned_tiles > 0 && mesh_plan && !list_dev) {
-        // Mesh scenes: the dispatch order of the work items -- whole tiles among themselves,
-        // then each chunk round's tiles among themselves (which tiles are whole and which
-        // chunked stays the raster-defined plan above, so no pixel's sums change).  A rank's
-        // first launch (or one after its tile ownership or plan changed) takes the static
-        // order (mesh_tile_cost's hull-hit classes, costliest first, raster order within a
-        // class); with tile_order 2 every launch also measures its items and
-        // tile_order_kernel writes the next launch's order from those durations.  (The
-        // kernels without meshes do not measure: see item_cost_add.)
-#if PTMI_STUDY
-        if (s->tile_order == 2 && !s->cost_dev) {
-            HIP_TRY(hipMalloc((void**)&s->cost_dev, (size_t)tiles * sizeof(unsigned long long)));
-            HIP_TRY(hipMemsetAsync(s->cost_dev, 0, (size_t)tiles * sizeof(unsigned long long), st));
-        }
-#endif
-        if (s->order_stride != tile_stride || s->order_offset != tile_offset || s->order_n != owned_tiles ||
-            s->order_tlist != tlist ||
-            s->order_whole != wp.n_whole) {
-            HIP_TRY(hipStreamSynchronize(st));  // order_host may still feed an earlier copy
-            mesh_tile_cost(s->tc_in, s->tile_cost, owned_tiles, owned_tile);  // this render's tiles, once
-            s->order_host.resize(owned_tiles);
-            for (uint32_t k = 0; k < wp.n_whole; k++) s->order_host[k] = k;
-            for (uint32_t k = 0; k < n_tail; k++) s->order_host[wp.n_whole + k] = k;
-            std::stable_sort(s->order_host.begin() + wp.n_whole, s->order_host.end(), [&](uint32_t a, uint32_t b) {
-                    return s->tile_cost[owned_tile(wp.n_whole + a)] > s->tile_cost[owned_tile(wp.n_whole + b)];
-                });
-            if (s->order_dev && s->order_cap < owned_tiles) {
-                HIP_TRY(hipFree(s->order_dev));
-                s->order_dev = nullptr;
-            }
-            if (!s->order_dev) {
-                HIP_TRY(hipMalloc((void**)&s->order_dev, (size_t)owned_tiles * sizeof(uint32_t)));
-                s->order_cap = owned_tiles;
-            }
-            HIP_TRY(hipMemcpyAsync(s->order_dev, s->order_host.data(), (size_t)owned_tiles * sizeof(uint32_t),
-                                   hipMemcpyHostToDevice, st));
-            s->order_stride = tile_stride;
-            s->order_offset = tile_offset;
-            s->order_n = owned_tiles;
-            s->order_tlist = tlist;
-            s->order_whole = wp.n_whole;
-        }
-        wp.order = s->order_dev;
-#if PTMI_STUDY
-        wp.cost = s->tile_order == 2 ? s->cost_dev : nullptr;
-#endif
-    }
-    if ((s->flags & 8) && s->dev.cam.aperture != 0 && s->sunf_samples != samples) {  // DoF table for this S
-        if (s->sunf) {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipFree(s->sunf));
-            s->sunf = nullptr;
-        }
-        HIP_TRY(hipMalloc((void**)&s->sunf, (size_t)samples * 2 * sizeof(double)));
-        HIP_TRY(launch_sunflower(s->sunf, samples, st));
-        s->sunf_samples = samples;
-    }
+    if (list_dev) plan.wp.tiles = list_dev;
+    else if ((rc = ensure_dispatch_order(s, plan, st, err, err_len))) return rc;
+    if ((rc = ensure_dof_table(s, samples, st, err, err_len))) return rc;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (s->timing) {
-        for (hipEvent_t* e : {&ev0, &ev1}) {
-            if (!s->spare.empty()) {
-                *e = s->spare.back();
-                s->spare.pop_back();
-            } else {
-                HIP_TRY(hipEventCreate(e));
-            }
-        }
-    }
+    if (s->timing && (rc = take_events(s, ev0, ev1, err, err_len))) return rc;
+    const size_t npix = (size_t)s->width * s->height;
     const bool partial_frame = tile_stride > 1 || list_dev;  // un-owned tiles
-    if (partial_frame) HIP_TRY(hipMemsetAsync(sums_dev, 0, (size_t)npix * 4 * sizeof(double), st));
-    if (partial_frame && sq_dev) HIP_TRY(hipMemsetAsync(sq_dev, 0, (size_t)npix * sizeof(double), st));
-    const bool planes = (s->flags & 1) == 0 || !split;  // partial layout (ptmi_kernels.hip store_sums)
-    // (moment renders: one more plane of partials, ptmi_kernels.hip store_mom)
-    const size_t need = (size_t)wp.n_tail * 64 * chunks * ((planes ? 3 : 4) + (sq_dev ? 1 : 0)) * sizeof(double);
-    if (need > s->partial_bytes) {
-        if (s->partial) {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipFree(s->partial));
-            s->partial = nullptr;
-            s->partial_bytes = 0;
-        }
-        HIP_TRY(hipMalloc((void**)&s->partial, need));
-        s->partial_bytes = need;
-    }
-    if (!split) {  // the launch's work-item counter, zeroed outside the timed span
+    if (partial_frame) HIP_TRY(hipMemsetAsync(sums_dev, 0, npix * 4 * sizeof(double), st));
+    if (partial_frame && sq_dev) HIP_TRY(hipMemsetAsync(sq_dev, 0, npix * sizeof(double), st));
+    HIP_TRY(s->partial.reserve(plan.partial_bytes, st));
+    if (!plan.split) {  // the launch's work-item counter, zeroed outside the timed span
         if (!s->item_ctr) HIP_TRY(hipMalloc((void**)&s->item_ctr, 256));
         HIP_TRY(hipMemsetAsync(s->item_ctr, 0, sizeof(uint32_t), st));
     }
     if (ev0) HIP_TRY(hipEventRecord(ev0, st));
 #if PTMI_STUDY
-    if (split) {
-        const int rc = render_split(s, samples, wp, seeds_dev, sums_dev, st, err, err_len);
-        if (rc) return rc;
+    if (plan.split) {
+        if ((rc = render_split(s, samples, wp, seeds_dev, sums_dev, st, err, err_len))) return rc;
     } else
 #endif
     {
-        HIP_TRY(launch_trace(s->dev, kflags | (sq_dev ? 512 : 0) /* F_MOM */, samples, wp, seeds_dev, s->sunf, sums_dev,
-                             s->partial, s->item_ctr, sq_dev, st));
+        HIP_TRY(launch_trace(s->dev, plan.kflags, samples, wp, seeds_dev, s->sunf, sums_dev, s->partial.p, s->item_ctr,
+                             sq_dev, st));
     }
     if (ev1) {
         HIP_TRY(hipEventRecord(ev1, st));
@@ -1315,9 +1153,10 @@ static int render_frame(ptmi_scene* s, uint32_t samples, uint32_t sample_begin, 
     }
 #if PTMI_STUDY
     // after the timed launch: the next launch's order from this one's item durations
-    if (wp.cost) HIP_TRY(launch_tile_order(wp.cost, wp.n_whole, wp.n_tail, tile_stride, tile_offset, s->order_dev, st));
+    if (wp.cost)
+        HIP_TRY(launch_tile_order(wp.cost, wp.n_whole, wp.n_tail, tile_stride, tile_offset, s->order_dev.p, st));
 #endif
-    HIP_TRY(launch_reduce(s->partial, sums_dev, wp, (int)W, (int)H, planes, sq_dev, st));
+    HIP_TRY(launch_reduce(s->partial.p, sums_dev, wp, (int)s->width, (int)s->height, plan.planes, sq_dev, st));
     return PTMI_OK;
 }
 
@@ -1469,9 +1308,9 @@ int ptmi_scene_set_rng(ptmi_scene* s, int mode, char* err, size_t err_len) {
         set_err(err, err_len, "ptmi_scene_set_rng: bad scene or mode %d", mode);
         return PTMI_ERR_ARG;
     }
-    if (mode == PTMI_RNG_XOSHIRO && (s->flags & (16 | 32))) {  // F_PROJ | F_TEX
+    if (mode == PTMI_RNG_XOSHIRO && (s->flags & (F_PROJ | F_TEX))) {
         set_err(err, err_len, "the statistical RNG mode exists for affine, untextured scenes only (this scene is %s)",
-                (s->flags & 32) ? "textured" : "not affine");
+                (s->flags & F_TEX) ? "textured" : "not affine");
         return PTMI_ERR_UNSUPPORTED;
     }
     s->rng = mode;
@@ -1494,7 +1333,7 @@ int ptmi_scene_set_camera(ptmi_scene* s, const void* camera, char* err, size_t e
         return PTMI_ERR_ARG;
     }
     const int flags = scene_flags(s->basis, cam);
-    if (s->rng == PTMI_RNG_XOSHIRO && (flags & (16 | 32))) {  // F_PROJ | F_TEX, as ptmi_scene_set_rng
+    if (s->rng == PTMI_RNG_XOSHIRO && (flags & (F_PROJ | F_TEX))) {  // as ptmi_scene_set_rng
         set_err(err, err_len, "the statistical RNG mode exists for affine scenes only (this camera is not affine)");
         return PTMI_ERR_UNSUPPORTED;
     }
@@ -1507,10 +1346,9 @@ int ptmi_scene_set_camera(ptmi_scene* s, const void* camera, char* err, size_t e
     HIP_TRY(launch_camera_terms(s->dev, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(resident_waves(s));  // the instantiation may have changed (F_DOF, F_PROJ): the work plan's size
-    if (s->flags & 1) {  // mesh scenes: the tile classes and the dispatch order built from them
+    if (s->flags & F_GROUPS) {  // mesh scenes: the tile classes are the view's
         s->tc_in.cam = cam;
-        s->tile_cost.clear();
-        s->order_n = 0;
+        s->drop_tile_classes();
     }
     return PTMI_OK;
 }
@@ -1556,9 +1394,9 @@ int ptmi_scene_set_objects(ptmi_scene* s, const void* objects, uint32_t n_obj, c
     SceneFlagBasis basis = s->basis;  // (forced, wide and the triangles' share stay)
     object_flag_basis(objs, basis.tris_affine, basis);
     const int flags = scene_flags(basis, s->dev.cam);
-    if (s->rng == PTMI_RNG_XOSHIRO && (flags & (16 | 32))) {  // F_PROJ | F_TEX, as ptmi_scene_set_rng
+    if (s->rng == PTMI_RNG_XOSHIRO && (flags & (F_PROJ | F_TEX))) {  // as ptmi_scene_set_rng
         set_err(err, err_len, "the statistical RNG mode exists for affine, untextured scenes only (these objects make "
-                              "the scene %s)", (flags & 32) ? "textured" : "not affine");
+                              "the scene %s)", (flags & F_TEX) ? "textured" : "not affine");
         return PTMI_ERR_UNSUPPORTED;
     }
     std::vector<PlaneRec> planes;
@@ -1608,12 +1446,11 @@ int ptmi_scene_set_objects(ptmi_scene* s, const void* objects, uint32_t n_obj, c
     HIP_TRY(launch_camera_terms(s->dev, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(resident_waves(s));  // the instantiation may have changed (F_MATERIALS, F_PROJ, F_TEX)
-    if (s->flags & 1) {  // mesh scenes: the group objects' inverses behind the tile classes
+    if (s->flags & F_GROUPS) {  // mesh scenes: the group objects' inverses behind the tile classes
         size_t j = 0;
         for (int k = run_end[3]; k < run_end[4] && j < s->tc_in.objs.size(); k++, j++)
             std::memcpy(s->tc_in.objs[j].inv, objs[k].inv, sizeof(s->tc_in.objs[j].inv));
-        s->tile_cost.clear();
-        s->order_n = 0;
+        s->drop_tile_classes();
     }
     return PTMI_OK;
 }
@@ -2056,17 +1893,6 @@ extern "C" int ptmi_stats_read(unsigned long long* out, int reset) { return ptmi
 #endif
 
 // ---- Diagnostics (include/ptmi_diag.h) -------------------------------------------------
-namespace ptmi {
-#if PTMI_STUDY
-hipError_t launch_walk(const DevScene& S, int flags, int mode, const WalkReq* req, uint32_t n, WalkRes* res,
-                       uint32_t* next, uint32_t grid, hipStream_t st);
-const void* walk_kernel_symbol(int mode);
-#endif
-hipError_t capture_setup(WalkReq* req, WalkRes* res, uint32_t cap);
-hipError_t capture_count(uint32_t* n);
-hipError_t timeline_setup(unsigned long long* buf, uint32_t cap);
-}  // namespace ptmi
-
 extern "C" int ptmi_diag_timeline_setup(void* buf_dev, uint32_t cap, char* err, size_t err_len) {
     const hipError_t e = timeline_setup((unsigned long long*)buf_dev, cap);
     if (e == hipErrorNotSupported) {
@@ -2156,7 +1982,7 @@ extern "C" int ptmi_diag_tile_cost(const void* objects, uint32_t n_obj, const vo
         set_err(err, err_len, "out holds %u tiles, the frame has %u", n_out, tiles);
         return PTMI_ERR_ARG;
     }
-    if (hs.flags & 1) {
+    if (hs.flags & F_GROUPS) {
         std::vector<uint8_t> c;
         mesh_tile_cost(tile_cost_input(hs), c, tiles, [](uint32_t k) { return k; });
         std::memcpy(out, c.data(), tiles);
@@ -2176,7 +2002,7 @@ extern "C" int ptmi_diag_scene_tile_cost(ptmi_scene* s, uint8_t* out, uint32_t n
         set_err(err, err_len, "out holds %u tiles, the frame has %u", n_out, tiles);
         return PTMI_ERR_ARG;
     }
-    if (s->flags & 1) {  // through the scene's own cache: the classes its next ordered render sorts by
+    if (s->flags & F_GROUPS) {  // through the scene's own cache: the classes its next ordered render sorts by
         mesh_tile_cost(s->tc_in, s->tile_cost, tiles, [](uint32_t k) { return k; });
         std::memcpy(out, s->tile_cost.data(), tiles);
     } else {
@@ -2256,13 +2082,13 @@ extern "C" int ptmi_diag_set_knob(ptmi_scene* s, int knob, int value) {
     if (!s) return PTMI_ERR_ARG;
     const uint32_t pos = (uint32_t)std::max(1, value);
     switch (knob) {
-    case PTMI_KNOB_TAIL_TILES: s->tail_tiles = (uint32_t)std::max(0, value); return PTMI_OK;
-    case PTMI_KNOB_TAIL_ITEMS: s->tail_items = pos; return PTMI_OK;
-    case PTMI_KNOB_MESH_ITEMS: s->mesh_items = pos; return PTMI_OK;
-    case PTMI_KNOB_MESH_ITEMS_SHARE: s->mesh_items_share = pos; return PTMI_OK;
-    case PTMI_KNOB_MIN_CHUNK: s->min_chunk = pos; return PTMI_OK;
-    case PTMI_KNOB_TAIL_SPLIT: s->tail_split = pos; return PTMI_OK;
-    case PTMI_KNOB_TAIL_MIN: s->tail_min = (uint32_t)std::max(0, value); return PTMI_OK;
+    case PTMI_KNOB_TAIL_TILES: s->knobs.tail_tiles = (uint32_t)std::max(0, value); return PTMI_OK;
+    case PTMI_KNOB_TAIL_ITEMS: s->knobs.tail_items = pos; return PTMI_OK;
+    case PTMI_KNOB_MESH_ITEMS: s->knobs.mesh_items = pos; return PTMI_OK;
+    case PTMI_KNOB_MESH_ITEMS_SHARE: s->knobs.mesh_items_share = pos; return PTMI_OK;
+    case PTMI_KNOB_MIN_CHUNK: s->knobs.min_chunk = pos; return PTMI_OK;
+    case PTMI_KNOB_TAIL_SPLIT: s->knobs.tail_split = pos; return PTMI_OK;
+    case PTMI_KNOB_TAIL_MIN: s->knobs.tail_min = (uint32_t)std::max(0, value); return PTMI_OK;
     case PTMI_KNOB_WALK_BATCH: s->dev.walk_batch = (int32_t)std::min<uint32_t>(pos, 64); return PTMI_OK;
     case PTMI_KNOB_HEMI_MESH: s->dev.hemi_mesh = value != 0; return PTMI_OK;
     case PTMI_KNOB_TILE_ORDER:
@@ -2270,7 +2096,7 @@ extern "C" int ptmi_diag_set_knob(ptmi_scene* s, int knob, int value) {
         // build compiles in (ptmi_kernels.hip PTMI_TILE_COST).
         if (value < 0 || value > (PTMI_STUDY ? 2 : 1)) return PTMI_ERR_UNSUPPORTED;
         s->tile_order = value;
-        s->order_n = 0;  // rebuild the order at the next render
+        s->drop_dispatch_order();
         return PTMI_OK;
 #if PTMI_STUDY
     case PTMI_KNOB_SPLIT_CHUNK: s->split_chunk = pos; return PTMI_OK;
@@ -2283,7 +2109,7 @@ extern "C" int ptmi_diag_set_knob(ptmi_scene* s, int knob, int value) {
 }
 
 extern "C" int ptmi_diag_force_flags(int flags) {
-    if (flags > 63) return PTMI_ERR_ARG;
+    if (flags > F_GENERIC) return PTMI_ERR_ARG;
     g_force_flags.store(flags < 0 ? -1 : flags);
     return PTMI_OK;
 }
@@ -2296,10 +2122,47 @@ extern "C" int ptmi_diag_denoise_variant(int variant) {
 extern "C" int ptmi_diag_hemi_mismatch(const ptmi_scene* s) { return s ? s->hemi_mismatch : -1; }
 
 extern "C" int ptmi_diag_scene_flags(const ptmi_scene* s) {
-    return s ? trace_kernel_flags(s->flags | (s->rng == PTMI_RNG_XOSHIRO ? 64 : 0)) : -1;
+    return s ? trace_kernel_flags(s->launch_flags()) : -1;
 }
 
 extern "C" int ptmi_diag_tile_ownership(const ptmi_scene* s, uint32_t tile_stride) {
     if (!s || tile_stride == 0) return -1;
-    return diagonal_tiles(s, tile_stride) ? 1 : 0;
+    return TileOwnership::diagonal(s->launch_flags(), s->width, tile_stride, s->plan_split_chunk() != 0) ? 1 : 0;
+}
+
+// The work plan of a request (ptmi_plan.h plan_work), with no scene and no device call.
+extern "C" int ptmi_diag_work_plan_host(const uint32_t* request, uint32_t n_request, uint64_t* plan_out,
+                                        uint32_t n_plan, uint32_t* tiles_out, uint32_t n_tiles, char* err,
+                                        size_t err_len) {
+    const uint32_t* q = request;
+    if (!q || !plan_out || n_request != PTMI_PLAN_REQUEST_WORDS || n_plan != PTMI_PLAN_WORDS ||
+        (n_tiles && !tiles_out) || q[0] == 0 || q[1] == 0 || (uint64_t)q[0] * q[1] > (uint64_t)1 << 30 ||
+        q[11] > (uint32_t)INT32_MAX) {
+        set_err(err, err_len, "ptmi_diag_work_plan_host: NULL pointer, %u request / %u plan words (%d / %d), or a bad "
+                              "frame or resident-wave count", n_request, n_plan, PTMI_PLAN_REQUEST_WORDS, PTMI_PLAN_WORDS);
+        return PTMI_ERR_ARG;
+    }
+    PlanRequest rq;
+    rq.width = q[0], rq.height = q[1];
+    rq.samples = q[2], rq.sample_begin = q[3], rq.sample_end = q[4];
+    rq.tile_stride = q[5], rq.tile_offset = q[6];
+    rq.chunks = q[7];
+    rq.has_list = q[8] != 0, rq.n_list = q[9];
+    rq.flags = (int)q[10];
+    rq.resident_waves = (int)q[11];
+    rq.moments = q[12] != 0;
+    rq.split_chunk = q[13];
+    PlanKnobs kn;
+    kn.tail_tiles = q[14], kn.tail_items = q[15], kn.mesh_items = q[16], kn.mesh_items_share = q[17];
+    kn.min_chunk = q[18], kn.tail_split = q[19], kn.tail_min = q[20];
+    PlanResult r;
+    if (const int rc = plan_work(rq, kn, r, err, err_len)) return rc;
+    const WorkPlan& wp = r.wp;
+    const uint64_t out[PTMI_PLAN_WORDS] = {wp.n_whole, wp.n_tail, wp.nchunks, wp.chunk_len, wp.n_long, wp.tail_len,
+                                           wp.s_begin, wp.s_end, wp.tile_stride, wp.tile_offset, r.owned_tiles,
+                                           (uint64_t)r.kflags, r.own.tlist, r.pooled, r.split, r.partial_bytes};
+    std::copy(out, out + PTMI_PLAN_WORDS, plan_out);
+    if (!rq.has_list)  // (a caller's list is the caller's)
+        for (uint32_t k = 0; k < n_tiles && k < r.owned_tiles; k++) tiles_out[k] = r.own(k);
+    return PTMI_OK;
 }

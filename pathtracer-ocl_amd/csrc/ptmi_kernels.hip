@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "ptmi_device.h"
+#include "ptmi_flags.h"
 #include "ptmi_camcull.h"
 #include "ptmi_sinf.h"
 #include "ptmi_fp64core.h"
@@ -106,6 +107,7 @@ __shared__ unsigned long long ptmi_wstat[1][64];
 #ifndef PTMI_STUDY
 #define PTMI_STUDY 0
 #endif
+#include "ptmi_launch.h"
 
 // The one round-6 instruction cut still behind a switch (the settled ones: DESIGN.md "settled switches").
 #ifndef PTMI_R6_NPAIR
@@ -498,27 +500,7 @@ __device__ __forceinline__ void consider(Hit& h, double t, int obj, int key) {
     }
 }
 
-// Scene-feature flags: the host inspects the records once and launches the
-// instantiation that compiles out absent object types / materials / DoF.  Every
-// type or material present in the scene keeps its flag, so the result is the
-// same as the generic path.
-enum : int {
-    F_GROUPS = 1,     // a type-4 object with BVH roots
-    F_CYLCUBE = 2,    // cylinders or cubes present
-    F_MATERIALS = 4,  // reflectivity != 0 or refractive index != 1 somewhere
-    F_DOF = 8,        // camera aperture != 0
-    F_ALL = 15,
-    F_PROJ = 16,      // not affine (see dotv): the literal double4 arithmetic, generic path only
-    F_TEX = 32,       // textured objects: with F_ALL | F_PROJ, the one textured instantiation
-    F_TLIST = 128,    // tile-split launch with an owned-tile list (WorkPlan::tiles): affine mesh kernels only
-    F_XRNG = 64,      // opt-in statistical mode (ptmi_scene_set_rng): xoshiro128** instead of noise3D,
-                      // affine instantiations only; never the parity path
-    F_MOM = 512,      // moment variant (ptmi_scene_render_moments): each finished path also adds
-                      // (r*r + g*g) + b*b of its accumColor into the pixel's second moment (mom_add)
-    F_WIDE = 256      // affine mesh scene whose child codes need 31 bits (>= 2^15 Node4s or triangles):
-                      // the affine kernel with a 32-bit LDS traversal stack (one F_ALL | F_WIDE
-                      // instantiation, +- F_XRNG; ADVICE r5: such scenes had been sent to F_PROJ)
-};
+// (The scene-feature flags F_* that select an instantiation: ptmi_flags.h.)
 
 // The camera ray's two anti-aliasing offsets of sample n (tracer.cl:869).
 template <int FL>
@@ -2280,7 +2262,7 @@ __device__ __forceinline__ const DevScene& scene_reload(const DevScene& S) {
 #define PTMI_POOL 1
 #endif
 template <int FL>
-constexpr bool kPoolOf = PTMI_POOL != 0 && (FL & F_GROUPS) != 0 && !(FL & (F_PROJ | F_XRNG));
+constexpr bool kPoolOf = PTMI_POOL != 0 && pool_kernel(FL);  // (F_TEX comes with F_PROJ in every instantiation)
 template <int FL>
 __device__ __forceinline__ void trace_groups(const DevScene& S0, uint32_t samples, const WorkPlan& WP,
                                              const double* __restrict__ seeds, const double* __restrict__ sunf,
@@ -3848,11 +3830,6 @@ static int kernel_flags(int flags) {
 }
 
 int trace_kernel_flags(int flags) { return kernel_flags(flags); }
-
-// Whether a launch with these scene flags can take an owned-tile list (ptmi_api.cpp render).
-bool tile_list_supported(int flags) {
-    return (flags & F_GROUPS) && !(flags & (F_PROJ | F_TEX | F_XRNG | F_WIDE));
-}
 
 const void* trace_kernel_symbol(int flags) {
     switch (kernel_flags(flags)) {

@@ -437,10 +437,6 @@ __global__ __launch_bounds__(kBlock, PTMI_WALK_WAVES) void walk_split_kernel(Dev
         }
 }
 
-bool split_supported(int flags) {
-    return (flags & F_GROUPS) && !(flags & (F_PROJ | F_TEX | F_XRNG | F_WIDE));
-}
-
 const void* trace_split_symbol(int flags) {
     switch (flags & F_ALL) {
 #define K(f) \
@@ -455,7 +451,7 @@ const void* walk_split_symbol() { return reinterpret_cast<const void*>(&walk_spl
 hipError_t launch_split_pass(const DevScene& S, int flags, uint32_t samples, const WorkPlan& WP, const SplitBufs& B,
                              const double* seeds, const double* sunf, double* part, uint32_t walk_grid,
                              hipStream_t st) {
-    if (!split_supported(flags)) return hipErrorInvalidValue;
+    if (!tile_list_supported(flags)) return hipErrorInvalidValue;  // the split form exists for the same scenes
     const dim3 grid((B.L + B.per_wave - 1) / B.per_wave), block(kBlock);
     switch (flags & F_ALL) {
 #define K(f)                                                                                                   \

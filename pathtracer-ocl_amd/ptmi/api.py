@@ -165,6 +165,9 @@ def load_library(path=None):
         lib.ptmi_diag_tile_cull.argtypes = [vp, vp, sz]
         lib.ptmi_diag_tile_cull_host.restype = i32
         lib.ptmi_diag_tile_cull_host.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, sz, cp, sz]
+    if hasattr(lib, "ptmi_diag_work_plan_host"):
+        lib.ptmi_diag_work_plan_host.restype = i32
+        lib.ptmi_diag_work_plan_host.argtypes = [vp, u32, vp, u32, vp, u32, cp, sz]
     lib.ptmi_finalize.restype = i32
     lib.ptmi_finalize.argtypes = [vp, vp, u32, u32, vp, cp, sz]
     lib.ptmi_fill_seeds.restype = i32
@@ -312,6 +315,32 @@ def tile_cull_host(objects, triangles, groups, camera):
                                                    _ptr(groups), len(groups), _ptr(camera),
                                                    out.ctypes.data_as(ctypes.c_void_p), len(out), err, len(err)), err)
     return out
+
+
+# ptmi_diag_work_plan_host: the request's words and the plan's, in the order include/ptmi_diag.h gives.
+PLAN_REQUEST_FIELDS = ("width", "height", "samples", "sample_begin", "sample_end", "tile_stride", "tile_offset",
+                       "chunks", "has_list", "n_list", "flags", "resident_waves", "moments", "split_chunk",
+                       "tail_tiles", "tail_items", "mesh_items", "mesh_items_share", "min_chunk", "tail_split",
+                       "tail_min")
+PLAN_FIELDS = ("n_whole", "n_tail", "nchunks", "chunk_len", "n_long", "tail_len", "s_begin", "s_end", "tile_stride",
+               "tile_offset", "owned_tiles", "launch_flags", "tlist", "pooled", "split", "partial_bytes")
+
+
+def work_plan_host(request, n_tiles=0):
+    """ptmi_diag_work_plan_host (host only, no scene): the work plan a render makes of `request` (a sequence of
+    the PLAN_REQUEST_FIELDS values, or a dict of them).  Returns ({PLAN_FIELDS name: value}, the first
+    min(n_tiles, owned_tiles) owned tiles' raster indices); raises PtmiError as the render would."""
+    if isinstance(request, dict):
+        request = [request[k] for k in PLAN_REQUEST_FIELDS]
+    req = np.ascontiguousarray(request, dtype=np.uint32)
+    plan = np.zeros(len(PLAN_FIELDS), dtype=np.uint64)
+    tiles = np.zeros(int(n_tiles), dtype=np.uint32)
+    err = ctypes.create_string_buffer(1024)
+    _check(load_library().ptmi_diag_work_plan_host(_ptr(req), len(req), _ptr(plan), len(plan), _ptr(tiles), len(tiles),
+                                                   err, len(err)), err)
+    d = {k: int(v) for k, v in zip(PLAN_FIELDS, plan)}
+    has_list = bool(req[PLAN_REQUEST_FIELDS.index("has_list")])  # (a caller's list is the caller's: no tiles)
+    return d, tiles[:0 if has_list else min(len(tiles), d["owned_tiles"])]
 
 
 class force_flags:

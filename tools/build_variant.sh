@@ -17,8 +17,10 @@ if [ "$NAME" = head ] || [ -n "$FROMREV" ]; then
   done
   # (the study kernels' file: revisions before the split keep that code in ptmi_kernels.hip)
   git show $REV:pathtracer-ocl_amd/csrc/ptmi_study_kernels.h > $SRC/ptmi_study_kernels.h 2>/dev/null || rm -f $SRC/ptmi_study_kernels.h
-  # (the tile classifier: revisions before the candidate masks have none)
-  git show $REV:pathtracer-ocl_amd/csrc/ptmi_camcull.h > $SRC/ptmi_camcull.h 2>/dev/null || rm -f $SRC/ptmi_camcull.h
+  # (the tile classifier, the motion records, the flags / launch / plan headers: older revisions have none)
+  for f in ptmi_camcull.h ptmi_motion.h ptmi_flags.h ptmi_launch.h ptmi_plan.h; do
+    git show $REV:pathtracer-ocl_amd/csrc/$f > $SRC/$f 2>/dev/null || rm -f $SRC/$f
+  done
   mkdir -p $(dirname $SRC)/../include
   for f in ptmi.h ptmi_diag.h ptmi_host.h; do
     git show $REV:include/$f > $(dirname $SRC)/../include/$f 2>/dev/null || true
