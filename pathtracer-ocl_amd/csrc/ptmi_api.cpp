@@ -157,7 +157,7 @@ struct ptmi_scene {
 // ptmi_diag_force_flags: kernel flags forced onto every scene created after the call
 // (-1: none).  Test hook for the generic instantiations.
 static std::atomic<int> g_force_flags{-1};
-// ptmi_diag_denoise_variant: the form of the a-trous pass (ptmi_kernels.hip launch_denoise).
+// ptmi_diag_denoise_variant: the form of the a-trous pass (ptmi_image_kernels.hip launch_denoise).
 static std::atomic<int> g_denoise_variant{1};  // the LDS form: 2.20 against 3.01 ms (profiles/denoise/SUMMARY.md)
 
 namespace {

@@ -10,6 +10,10 @@
 // reference's OpenCL builtins resolve to (ocml sin_f32 / sin/cos/pow/sqrt/rsqrt
 // f64, maxnum/minnum), so on the same inputs the image matches the reference
 // kernel bit-for-bit in practice (tests/test_gpu_parity.py).
+//
+// Only the tracer is here: trace_kernel<FL>, the per-scene preparation kernels that share its device
+// code, the chunk reduce that ends a trace launch, and their launch wrappers.  The image-space passes
+// (denoiser, reprojection, error map, finalize, ...) are in ptmi_image_kernels.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -2128,11 +2132,19 @@ __device__ __forceinline__ void chunk_range(const WorkPlan& WP, uint32_t c, uint
 // launch has one (ptmi_scene_render_tiles), else the stride -- a wave-uniform select, so the plain
 // instantiations, which never take a caller's list, keep their code.
 enum : int { kTilesStride = 0, kTilesList = 1, kTilesSelect = 2 };
+constexpr int tiles_of(int fl) {
+    return (fl & F_TLIST) ? kTilesList : ((fl & F_MOM) && !tile_list_supported(fl)) ? kTilesSelect : kTilesStride;
+}
 template <int FL>
-constexpr int kTilesOf = (FL & F_TLIST) ? kTilesList
-                         : ((FL & F_MOM) && !((FL & F_GROUPS) && !(FL & (F_PROJ | F_TEX | F_XRNG | F_WIDE))))
-                             ? kTilesSelect
-                             : kTilesStride;
+constexpr int kTilesOf = tiles_of(FL);
+// (the families without F_TLIST forms used to be spelled out here: the same truth table)
+static_assert([] {
+    for (int fl = 0; fl < 1024; fl++)
+        if (((fl & F_MOM) && !tile_list_supported(fl)) !=
+            ((fl & F_MOM) && !((fl & F_GROUPS) && !(fl & (F_PROJ | F_TEX | F_XRNG | F_WIDE)))))
+            return false;
+    return true;
+}(), "kTilesOf: tile_list_supported() is no longer the families that have F_TLIST instantiations");
 template <int kTiles = kTilesStride>
 __device__ __forceinline__ Item work_item(const DevScene& S, const WorkPlan& WP, uint32_t item, int lane) {
     Item it{};
@@ -3205,366 +3217,6 @@ hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st) {
     return hipGetLastError();
 }
 
-// ---- The a-trous denoiser (ptmi_denoise) ------------------------------------------------------
-// An edge-avoiding wavelet filter steered by the first-hit records and the pixels' variance.  The
-// state is (r, g, b, var) per pixel, ping-ponged between the two halves of the caller's workspace:
-// denoise_start forms it, denoise_pass runs once per step 2^i, denoise_end writes the frame.  Every
-// FP64 operation is separately rounded and in the order ptmi/denoise.py atrous_reference states;
-// exp is the one operation numpy may round differently.
-struct DenoiseArgs {
-    int W, H, step, npow;
-    double sigma_l, sigma_d;
-};
-// A tap: its state, and of its record the position, the normal and the object id.
-struct DnTap {
-    double c0, c1, c2, v, x0, x1, x2, n0, n1, n2, id;
-};
-__device__ __forceinline__ double dn_lum(double r, double g, double b) { return (0.2126 * r + 0.7152 * g) + 0.0722 * b; }
-__device__ __forceinline__ double dn_floor(double a) { return a > 1e-3 ? a : 1e-3; }  // (NaN: the floor)
-__device__ __forceinline__ bool dn_finite(double a, double b, double c, double d) {
-    return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);
-}
-
-__global__ __launch_bounds__(256) void denoise_start(const double* __restrict__ rgba, const double* __restrict__ se,
-                                                     const double* __restrict__ feat, double* __restrict__ state,
-                                                     uint32_t npix, bool demod) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const double2* p = reinterpret_cast<const double2*>(rgba + 4 * (size_t)i);
-    const double2* f = reinterpret_cast<const double2*>(feat + 12 * (size_t)i);
-    const double2 p0 = p[0], p1 = p[1], a0 = f[4], a1 = f[5];
-    const double s = se[i];
-    double r = p0.x, g = p0.y, b = p1.x, v = s * s;
-    if (demod) {
-        const double m = dn_floor(dn_lum(a0.x, a0.y, a1.x));
-        r = r / dn_floor(a0.x);
-        g = g / dn_floor(a0.y);
-        b = b / dn_floor(a1.x);
-        v = v / (m * m);
-    }
-    double2* o = reinterpret_cast<double2*>(state + 4 * (size_t)i);
-    o[0] = make_double2(r, g);
-    o[1] = make_double2(b, v);
-}
-
-__global__ __launch_bounds__(256) void denoise_end(const double* __restrict__ state, const double* __restrict__ rgba,
-                                                   const double* __restrict__ se, const double* __restrict__ feat,
-                                                   double* __restrict__ out, double* __restrict__ out_se, uint32_t npix,
-                                                   bool demod) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const double2* p = reinterpret_cast<const double2*>(rgba + 4 * (size_t)i);
-    const double2* q = reinterpret_cast<const double2*>(state + 4 * (size_t)i);
-    const double2* f = reinterpret_cast<const double2*>(feat + 12 * (size_t)i);
-    const double2 p0 = p[0], p1 = p[1], q0 = q[0], q1 = q[1], a0 = f[4], a1 = f[5];
-    const double s = se[i];
-    double r = q0.x, g = q0.y, b = q1.x, e = sqrt(q1.y);
-    if (demod) {
-        r = r * dn_floor(a0.x);
-        g = g * dn_floor(a0.y);
-        b = b * dn_floor(a1.x);
-        e = e * dn_floor(dn_lum(a0.x, a0.y, a1.x));
-    }
-    if (!dn_finite(p0.x, p0.y, p1.x, s)) r = p0.x, g = p0.y, b = p1.x, e = s;  // such a pixel passes through
-    double2* o = reinterpret_cast<double2*>(out + 4 * (size_t)i);
-    o[0] = make_double2(r, g);
-    o[1] = make_double2(b, 1.0);
-    if (out_se) out_se[i] = e;
-}
-
-// One pass, one thread per pixel on kDnX x kDnY blocks.  kLdsStep == 0: every tap is a global gather
-// (two 16-B loads of state, four of the record).  kLdsStep == 1, 2: the pass at that step with the
-// block's pixels and their halo of 2 * step staged in LDS first, 11 planes of doubles; the arithmetic
-// is the same, so the two forms give the same bits.
-static constexpr int kDnX = 16, kDnY = 16;
-template <int kLdsStep>
-__global__ __launch_bounds__(kDnX * kDnY) void denoise_pass(const double* __restrict__ sin,
-                                                            const double* __restrict__ feat,
-                                                            double* __restrict__ sout, DenoiseArgs a) {
-    constexpr bool kLds = kLdsStep != 0;
-    constexpr int kHalo = 2 * kLdsStep, kTW = kDnX + 2 * kHalo, kTH = kDnY + 2 * kHalo;
-    __shared__ double lds[kLds ? 11 : 1][kLds ? kTW * kTH : 1];
-    const int W = a.W, H = a.H, step = kLds ? kLdsStep : a.step;
-    const int bx0 = (int)blockIdx.x * kDnX, by0 = (int)blockIdx.y * kDnY;
-    const int x = bx0 + (int)threadIdx.x % kDnX, y = by0 + (int)threadIdx.x / kDnX;
-    auto gtap = [&](int qx, int qy) {
-        const size_t i = (size_t)qy * W + qx;
-        const double2* s = reinterpret_cast<const double2*>(sin + 4 * i);
-        const double2* f = reinterpret_cast<const double2*>(feat + 12 * i);
-        const double2 s0 = s[0], s1 = s[1], f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
-        return DnTap{s0.x, s0.y, s1.x, s1.y, f0.x, f0.y, f1.x, f2.x, f2.y, f3.x, f3.y};
-    };
-    if constexpr (kLds) {  // in-image pixels of the tile; the others are never read (their taps are skipped)
-        for (int k = (int)threadIdx.x; k < kTW * kTH; k += kDnX * kDnY) {
-            const int qx = bx0 - kHalo + k % kTW, qy = by0 - kHalo + k / kTW;
-            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-            const DnTap T = gtap(qx, qy);
-            lds[0][k] = T.c0, lds[1][k] = T.c1, lds[2][k] = T.c2, lds[3][k] = T.v;
-            lds[4][k] = T.x0, lds[5][k] = T.x1, lds[6][k] = T.x2;
-            lds[7][k] = T.n0, lds[8][k] = T.n1, lds[9][k] = T.n2, lds[10][k] = T.id;
-        }
-        __syncthreads();
-    }
-    if (x >= W || y >= H) return;
-    auto tap = [&](int qx, int qy) {
-        if constexpr (kLds) {
-            const int k = (qy - by0 + kHalo) * kTW + (qx - bx0 + kHalo);
-            return DnTap{lds[0][k], lds[1][k], lds[2][k], lds[3][k], lds[4][k], lds[5][k],
-                         lds[6][k], lds[7][k], lds[8][k], lds[9][k], lds[10][k]};
-        } else {
-            return gtap(qx, qy);
-        }
-    };
-    // the state and the id alone (the variance prefilter's taps)
-    auto tap_s = [&](int qx, int qy) {
-        if constexpr (kLds) {
-            const int k = (qy - by0 + kHalo) * kTW + (qx - bx0 + kHalo);
-            return DnTap{lds[0][k], lds[1][k], lds[2][k], lds[3][k], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, lds[10][k]};
-        } else {
-            const size_t i = (size_t)qy * W + qx;
-            const double2* s = reinterpret_cast<const double2*>(sin + 4 * i);
-            const double2 s0 = s[0], s1 = s[1];
-            return DnTap{s0.x, s0.y, s1.x, s1.y, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, feat[12 * i + 7]};
-        }
-    };
-    const size_t i = (size_t)y * W + x;
-    const DnTap P = tap(x, y);
-    double2* o = reinterpret_cast<double2*>(sout + 4 * i);
-    if (!dn_finite(P.c0, P.c1, P.c2, P.v)) {  // passes through
-        o[0] = make_double2(P.c0, P.c1);
-        o[1] = make_double2(P.c2, P.v);
-        return;
-    }
-    const bool miss = P.id < 0.0;
-    // the variance around p: 3x3 (1/4, 1/8, 1/16) at distance 1 over the taps the filter itself would take
-    double sv = 0.0, sk = 0.0;
-#pragma unroll
-    for (int gy = 0; gy < 3; gy++) {
-#pragma unroll
-        for (int gx = 0; gx < 3; gx++) {
-            const double k = (gx == 1 ? 0.5 : 0.25) * (gy == 1 ? 0.5 : 0.25);
-            const int qx = x + gx - 1, qy = y + gy - 1;
-            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-            const DnTap Q = tap_s(qx, qy);
-            if (!dn_finite(Q.c0, Q.c1, Q.c2, Q.v) || (Q.id < 0.0) != miss) continue;
-            sv = sv + k * Q.v;
-            sk = sk + k;
-        }
-    }
-    const double vbar = sv / sk;
-    const double sd = a.sigma_l * sqrt(vbar < 0.0 ? 0.0 : vbar) + 1e-12;
-    const double dd_den = a.sigma_d * feat[12 * i + 3] + 1e-12;
-    const double lp = dn_lum(P.c0, P.c1, P.c2);
-    double sw = 0.0, s2 = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0;
-#pragma unroll
-    for (int iy = 0; iy < 5; iy++) {
-#pragma unroll
-        for (int ix = 0; ix < 5; ix++) {
-            const double hx = ix == 2 ? 0.375 : (ix == 1 || ix == 3) ? 0.25 : 0.0625;
-            const double hy = iy == 2 ? 0.375 : (iy == 1 || iy == 3) ? 0.25 : 0.0625;
-            const double hh = hx * hy;
-            const int qx = x + (ix - 2) * step, qy = y + (iy - 2) * step;
-            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-            const DnTap Q = tap(qx, qy);
-            if (!dn_finite(Q.c0, Q.c1, Q.c2, Q.v) || (Q.id < 0.0) != miss) continue;
-            double w = hh;
-            if (!(ix == 2 && iy == 2)) {
-                const double wl = exp(-(fabs(lp - dn_lum(Q.c0, Q.c1, Q.c2)) / sd));
-                if (miss) {
-                    w = hh * wl;
-                } else {
-                    const double dn = (P.n0 * Q.n0 + P.n1 * Q.n1) + P.n2 * Q.n2;
-                    double wn = dn > 0.0 ? dn : 0.0;
-                    for (int k = 0; k < a.npow; k++) wn = wn * wn;
-                    const double dd = (P.n0 * (Q.x0 - P.x0) + P.n1 * (Q.x1 - P.x1)) + P.n2 * (Q.x2 - P.x2);
-                    const double wd = exp(-(fabs(dd) / dd_den));
-                    w = ((hh * wn) * wd) * wl;
-                }
-            }
-            sw = sw + w;
-            s2 = s2 + (w * w) * Q.v;
-            r0 = r0 + w * (Q.c0 - P.c0);
-            r1 = r1 + w * (Q.c1 - P.c1);
-            r2 = r2 + w * (Q.c2 - P.c2);
-        }
-    }
-    // the weighted mean written around c_p: equal colours stay equal bit for bit
-    o[0] = make_double2(P.c0 + r0 / sw, P.c1 + r1 / sw);
-    o[1] = make_double2(P.c2 + r2 / sw, s2 / (sw * sw));
-}
-
-// work: two states of npix * 4 doubles.  variant (ptmi_diag_denoise_variant): 0 every pass gathers from
-// global memory; 1 the passes at steps 1 and 2 stage their tile in LDS.
-hipError_t launch_denoise(const double* rgba, const double* se, const double* feat, uint32_t W, uint32_t H,
-                          uint32_t iterations, bool demod, double sigma_l, double sigma_d, uint32_t npow, double* out,
-                          double* out_se, double* work, int variant, hipStream_t st) {
-    const uint32_t npix = W * H;
-    double* cur = work;
-    double* nxt = work + 4 * (size_t)npix;
-    hipLaunchKernelGGL(denoise_start, dim3((npix + 255) / 256), dim3(256), 0, st, rgba, se, feat, cur, npix, demod);
-    const dim3 grid((W + kDnX - 1) / kDnX, (H + kDnY - 1) / kDnY), block(kDnX * kDnY);
-    for (uint32_t i = 0; i < iterations; i++) {
-        const DenoiseArgs a{(int)W, (int)H, 1 << i, (int)npow, sigma_l, sigma_d};
-        if (variant == 1 && i == 0)
-            hipLaunchKernelGGL(denoise_pass<1>, grid, block, 0, st, cur, feat, nxt, a);
-        else if (variant == 1 && i == 1)
-            hipLaunchKernelGGL(denoise_pass<2>, grid, block, 0, st, cur, feat, nxt, a);
-        else
-            hipLaunchKernelGGL(denoise_pass<0>, grid, block, 0, st, cur, feat, nxt, a);
-        double* tmp = cur;
-        cur = nxt;
-        nxt = tmp;
-    }
-    hipLaunchKernelGGL(denoise_end, dim3((npix + 255) / 256), dim3(256), 0, st, cur, rgba, se, feat, out, out_se, npix,
-                       demod);
-    return hipGetLastError();
-}
-
-// ---- Temporal accumulation (ptmi_reproject) ----------------------------------------------------
-// One thread per pixel on the denoise passes' 16 x 16 blocks: a wave covers 4 rows of 16 pixels, so
-// its own loads and stores are 512-B (frame) and 1-KB (history) runs of 16-B accesses, and its taps
-// into the previous frame -- neighbouring pixels project to neighbouring places -- stay within a few
-// rows.  Per pixel 136 B of its own frame, up to four taps of 48 B history and 64 B of a record, 64 B
-// (+ 40 B) out: bandwidth-bound, no LDS.  Every FP64 operation is separately rounded and in the
-// order ptmi/temporal.py reproject_reference states; the matrix, the camera scalars and the
-// thresholds are by-value arguments (scalar registers).
-//
-// kMotion (ptmi_reproject_motion): the pixel's object may have moved since the previous frame.  Its
-// motion record (include/ptmi.h ptmi_motion_table, 192 B) is read per lane by the pixel's id -- ids are
-// not wave-uniform -- as 16-B vector loads; a moved object's point and normal are carried back to where
-// they were (x' = B (x_p, 1), n' = G n_p / |G n_p|) before the projection and the tap tests, a static
-// one (or an id outside the table) takes the path below with the current point, bit for bit, and an
-// object without a usable motion resets.  The instantiation without kMotion ignores the two trailing
-// arguments and keeps the instruction stream it had as a plain kernel.
-template <bool kMotion>
-__global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __restrict__ rgba,
-                                                                const double* __restrict__ se,
-                                                                const double* __restrict__ feat,
-                                                                const double* __restrict__ prev_hist,
-                                                                const double* __restrict__ prev_feat,
-                                                                ReprojectArgs a, double* __restrict__ out_hist,
-                                                                double* __restrict__ out_rgba,
-                                                                double* __restrict__ out_se,
-                                                                const double* __restrict__ motion, int n_obj) {
-    const int W = a.W, H = a.H;
-    const int x = (int)blockIdx.x * kDnX + (int)threadIdx.x % kDnX, y = (int)blockIdx.y * kDnY + (int)threadIdx.x / kDnX;
-    if (x >= W || y >= H) return;
-    const size_t i = (size_t)y * W + x;
-    const double2* p = reinterpret_cast<const double2*>(rgba + 4 * i);
-    const double2* f = reinterpret_cast<const double2*>(feat + 12 * i);
-    const double2 p0 = p[0], p1 = p[1], f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
-    const double s = se[i];
-    const double c0 = p0.x, c1 = p0.y, c2 = p1.x;
-    const double px = f0.x, py = f0.y, pz = f1.x, pt = f1.y, n0 = f2.x, n1 = f2.y, n2 = f3.x, id = f3.y;
-    const double v = s * s;
-    const bool fin = dn_finite(c0, c1, c2, s);
-    // the reset: this frame alone (a pixel that is not finite is no history for the next frame)
-    double o0 = c0, o1 = c1, o2 = c2, ov = v, on = fin ? 1.0 : 0.0;
-    if (prev_hist != nullptr && fin && !(id < 0.0)) {
-        // the surface point and its normal as the previous frame saw them
-        double ux = px, uy = py, uz = pz, m0 = n0, m1 = n1, m2 = n2;
-        bool history = true;
-        if (kMotion) {
-            if (id < (double)n_obj) {  // (id >= 0 here; a NaN id fails and stays static)
-                const double2* mr = reinterpret_cast<const double2*>(motion + 24 * (int)id);
-                const double state = mr[10].y;
-                if (state == 1.0) {
-                    const double2 b0 = mr[0], b1 = mr[1], b2 = mr[2], b3 = mr[3], b4 = mr[4], b5 = mr[5];
-                    const double2 g0 = mr[6], g1 = mr[7], g2 = mr[8], g3 = mr[9], g4 = mr[10];
-                    ux = ((b0.x * px + b0.y * py) + b1.x * pz) + b1.y;
-                    uy = ((b2.x * px + b2.y * py) + b3.x * pz) + b3.y;
-                    uz = ((b4.x * px + b4.y * py) + b5.x * pz) + b5.y;
-                    const double e0 = (g0.x * n0 + g0.y * n1) + g1.x * n2;
-                    const double e1 = (g1.y * n0 + g2.x * n1) + g2.y * n2;
-                    const double e2 = (g3.x * n0 + g3.y * n1) + g4.x * n2;
-                    const double l = (e0 * e0 + e1 * e1) + e2 * e2;
-                    history = l > 0.0 && isfinite(l);
-                    const double len = sqrt(l);
-                    m0 = e0 / len;
-                    m1 = e1 / len;
-                    m2 = e2 / len;
-                } else if (state != 0.0) {
-                    history = false;
-                }
-            }
-        }
-        const double* T = a.T;
-        const double qx = ((T[0] * ux + T[1] * uy) + T[2] * uz) + T[3];
-        const double qy = ((T[4] * ux + T[5] * uy) + T[6] * uz) + T[7];
-        const double z = -(((T[8] * ux + T[9] * uy) + T[10] * uz) + T[11]);
-        if (history && z > 0.0) {
-            const double fu = (a.half_width - qx / z) / a.pixel_size - 0.5;
-            const double fv = (a.half_height - qy / z) / a.pixel_size - 0.5;
-            const double fx0 = floor(fu), fy0 = floor(fv);
-            const double wx = fu - fx0, wy = fv - fy0;
-            const double bound = a.plane_dist * pt;
-            double sw = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0, sv = 0.0, sn = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {  // taps (0,0), (1,0), (0,1), (1,1)
-                const int ti = k & 1, tj = k >> 1;
-                const double tx = fx0 + (double)ti, ty = fy0 + (double)tj;
-                // in double: a NaN or a huge coordinate fails the test before any conversion
-                if (!(tx >= 0.0 && tx < (double)W && ty >= 0.0 && ty < (double)H)) continue;
-                const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
-                const double2* hq = reinterpret_cast<const double2*>(prev_hist + 8 * q);
-                const double2 h0 = hq[0], h1 = hq[1], h2 = hq[2];
-                if (!(h2.x > 0.0) || !dn_finite(h0.x, h0.y, h1.x, h1.y)) continue;
-                const double2* fq = reinterpret_cast<const double2*>(prev_feat + 12 * q);
-                const double2 g0 = fq[0], g1 = fq[1], g2 = fq[2], g3 = fq[3];
-                if (g3.y != id) continue;
-                const double dn = (m0 * g2.x + m1 * g2.y) + m2 * g3.x;
-                if (!(dn >= a.normal_cos)) continue;
-                const double dd = (m0 * (g0.x - ux) + m1 * (g0.y - uy)) + m2 * (g1.x - uz);
-                if (!(fabs(dd) <= bound)) continue;
-                const double w = (ti ? wx : 1.0 - wx) * (tj ? wy : 1.0 - wy);
-                sw = sw + w;
-                r0 = r0 + w * (h0.x - c0);
-                r1 = r1 + w * (h0.y - c1);
-                r2 = r2 + w * (h1.x - c2);
-                sv = sv + (w * w) * h1.y;
-                sn = sn + w * h2.x;
-            }
-            if (sw >= a.min_weight && sw > 0.0) {
-                // the history's weighted mean written around this frame's colour, and the blend around
-                // the history: a constant sequence stays constant bit for bit
-                const double h0 = c0 + r0 / sw, h1 = c1 + r1 / sw, h2 = c2 + r2 / sw;
-                const double hv = sv / (sw * sw), hn = sn / sw;
-                const double np1 = hn + 1.0;
-                on = np1 < a.max_history ? np1 : a.max_history;
-                const double al = 1.0 / on, be = 1.0 - al;
-                o0 = h0 + al * (c0 - h0);
-                o1 = h1 + al * (c1 - h1);
-                o2 = h2 + al * (c2 - h2);
-                ov = (al * al) * v + (be * be) * hv;
-            }
-        }
-    }
-    double2* oh = reinterpret_cast<double2*>(out_hist + 8 * i);
-    oh[0] = make_double2(o0, o1);
-    oh[1] = make_double2(o2, ov);
-    oh[2] = make_double2(on, 0.0);
-    oh[3] = make_double2(0.0, 0.0);
-    if (out_rgba) {
-        double2* o = reinterpret_cast<double2*>(out_rgba + 4 * i);
-        o[0] = make_double2(o0, o1);
-        o[1] = make_double2(o2, 1.0);
-    }
-    if (out_se) out_se[i] = sqrt(ov);
-}
-
-hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
-                            const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
-                            double* out_se, const double* motion, int32_t n_obj, hipStream_t st) {
-    const dim3 grid(((uint32_t)a.W + kDnX - 1) / kDnX, ((uint32_t)a.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
-    if (motion)
-        hipLaunchKernelGGL(reproject_pass<true>, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
-                           out_rgba, out_se, motion, (int)n_obj);
-    else
-        hipLaunchKernelGGL(reproject_pass<false>, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
-                           out_rgba, out_se, motion, 0);
-    return hipGetLastError();
-}
-
 // The tail tiles' chunk partials (WorkPlan) summed in chunk order (deterministic)
 // into the frame; one thread per tail-tile pixel.  kMom (moment renders): the chunk items' second
 // moments (store_mom's plane) summed in chunk order likewise, into sq.
@@ -3613,234 +3265,20 @@ __global__ __launch_bounds__(256) void reduce_chunks_kernel(const double* __rest
     if constexpr (kMom) sq[(size_t)py * W + px] = m2;
 }
 
-// ---- error map and accumulate (ptmi_error_map, ptmi_accumulate) ------------------------------
-// A pixel's standard error from its sums record (r, g, b, n) and second moment (ptmi/error.py
-// error_map_reference restates this operation for operation):
-//   n == 0: se = 0 (not owned);  n == 1: se = +inf;  else
-//   d = sq / n - ((mr*mr + mg*mg) + mb*mb),  var = max(d, 0) * (n / (n - 1)),  se2 = var / n,  se = sqrt(se2)
-// counted: n >= 2 (the pixels the summaries run over).  A NaN d stays NaN.
-struct PixelErr {
-    double se, se2, mean;
-    bool counted;
-};
-__device__ __forceinline__ PixelErr pixel_err(const double* __restrict__ sums, const double* __restrict__ sq,
-                                              size_t i) {
-    PixelErr e{0.0, 0.0, 0.0, false};
-    const double n = sums[4 * i + 3];
-    if (n == 0.0) return e;
-    if (n == 1.0) {
-        e.se = __builtin_inf();
-        return e;
-    }
-    const double mr = sums[4 * i + 0] / n, mg = sums[4 * i + 1] / n, mb = sums[4 * i + 2] / n;
-    const double d = sq[i] / n - ((mr * mr + mg * mg) + mb * mb);
-    const double var = (d < 0.0 ? 0.0 : d) * (n / (n - 1.0));
-    e.se2 = var / n;
-    e.se = sqrt(e.se2);
-    e.mean = ((mr + mg) + mb) / 3.0;
-    e.counted = true;
-    return e;
-}
-// A fixed-shape tree over the workgroup's kN slots (kN a power of two): the same inputs give the
-// same bits.  v[0] sums, v[1] maxima, v[2] sums, v[3] sums.
-template <int kN>
-__device__ __forceinline__ void err_tree(double (*v)[kN], int t) {
-    for (int s = kN / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) {
-            v[0][t] = v[0][t] + v[0][t + s];
-            v[1][t] = v[1][t + s] > v[1][t] ? v[1][t + s] : v[1][t];
-            v[2][t] = v[2][t] + v[2][t + s];
-            v[3][t] = v[3][t] + v[3][t + s];
-        }
-    }
-    __syncthreads();
-}
-// One wave per 8x8 tile (kTile; raster order): se per pixel, the tile's rms se, and the tile's
-// (sum se2, max finite se, sum mean, count) into tile_part for error_stats.
-__global__ __launch_bounds__(64) void error_map(const double* __restrict__ sums, const double* __restrict__ sq, int W,
-                                                int H, double* __restrict__ se, double* __restrict__ tile_err,
-                                                double* __restrict__ tile_part) {
-    __shared__ double v[4][64];
-    const int t = threadIdx.x, tiles_x = (W + kTile - 1) / kTile;
-    const int px = (int)(blockIdx.x % (uint32_t)tiles_x) * kTile + (t & 7);
-    const int py = (int)(blockIdx.x / (uint32_t)tiles_x) * kTile + (t >> 3);
-    PixelErr e{0.0, 0.0, 0.0, false};
-    if (px < W && py < H) {
-        const size_t i = (size_t)py * W + px;
-        e = pixel_err(sums, sq, i);
-        if (se) se[i] = e.se;
-    }
-    v[0][t] = e.counted ? e.se2 : 0.0;
-    v[1][t] = (e.counted && e.se < __builtin_inf()) ? e.se : 0.0;  // (a NaN se compares false)
-    v[2][t] = e.counted ? e.mean : 0.0;
-    v[3][t] = e.counted ? 1.0 : 0.0;
-    err_tree<64>(v, t);
-    if (t == 0) {
-        if (tile_err) tile_err[blockIdx.x] = v[3][0] > 0.0 ? sqrt(v[0][0] / v[3][0]) : 0.0;
-        for (int k = 0; k < 4; k++) tile_part[4 * (size_t)blockIdx.x + k] = v[k][0];
-    }
-}
-// The frame's summaries from the tiles' (one workgroup): thread t folds tiles t, t + 256, ... in
-// that order, then the tree.  stats: rms se, max finite se, mean of the pixel means, pixel count.
-__global__ __launch_bounds__(256) void error_stats(const double* __restrict__ tile_part, uint32_t tiles,
-                                                   double* __restrict__ stats) {
-    __shared__ double v[4][256];
-    const int t = threadIdx.x;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (uint32_t k = (uint32_t)t; k < tiles; k += 256u) {
-        const double* p = tile_part + 4 * (size_t)k;
-        a0 = a0 + p[0];
-        a1 = p[1] > a1 ? p[1] : a1;
-        a2 = a2 + p[2];
-        a3 = a3 + p[3];
-    }
-    v[0][t] = a0;
-    v[1][t] = a1;
-    v[2][t] = a2;
-    v[3][t] = a3;
-    err_tree<256>(v, t);
-    if (t == 0) {
-        const double cnt = v[3][0];
-        stats[0] = cnt > 0.0 ? sqrt(v[0][0] / cnt) : 0.0;
-        stats[1] = v[1][0];
-        stats[2] = cnt > 0.0 ? v[2][0] / cnt : 0.0;
-        stats[3] = cnt;
-    }
-}
-// dst[k] += src[k] (frame sums, counts included, and second moments of successive batches).
-__global__ __launch_bounds__(256) void accumulate_sums(double* __restrict__ dst, const double* __restrict__ src,
-                                                       size_t n) {
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) dst[k] = dst[k] + src[k];
-}
-
-// colors * (1.0 / samples), alpha 1 (tracer.cl:837, 1184-1187).
-__global__ __launch_bounds__(256) void finalize_kernel(const double* __restrict__ sums, double* __restrict__ out,
-                                                       uint32_t npix, uint32_t samples) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const double w = 1.0 / samples;
-    out[4 * (size_t)i + 0] = sums[4 * (size_t)i + 0] * w;
-    out[4 * (size_t)i + 1] = sums[4 * (size_t)i + 1] * w;
-    out[4 * (size_t)i + 2] = sums[4 * (size_t)i + 2] * w;
-    out[4 * (size_t)i + 3] = 1.0;
-}
-
-// finalize_kernel with each pixel's own sample count n = sums[4i + 3] (adaptive renders): the same
-// multiply by 1.0 / n, so a uniform count gives finalize_kernel's bits; n == 0 -> RGB 0.  Alpha 1.
-__global__ __launch_bounds__(256) void finalize_counts(const double* __restrict__ sums,
-                                                              double* __restrict__ out, uint32_t npix) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const double n = sums[4 * (size_t)i + 3];
-    const double w = 1.0 / n;
-    out[4 * (size_t)i + 0] = n == 0.0 ? 0.0 : sums[4 * (size_t)i + 0] * w;
-    out[4 * (size_t)i + 1] = n == 0.0 ? 0.0 : sums[4 * (size_t)i + 1] * w;
-    out[4 * (size_t)i + 2] = n == 0.0 ? 0.0 : sums[4 * (size_t)i + 2] * w;
-    out[4 * (size_t)i + 3] = 1.0;
-}
-
-// The tiles that still need samples (ptmi_select_tiles): candidate j is in_tiles[j] (or j itself,
-// in_tiles == nullptr), kept iff tile_err[candidate] > threshold -- a NaN error and a tie are
-// dropped, +inf is kept -- and the kept ones go to out_tiles in candidate order, their number to
-// count[0].  One workgroup walks the candidates in blocks of kSelectBlock, in order: each wave
-// ballots its 64 keeps, the waves' counts meet in LDS, and a kept candidate's position is the
-// running base plus the earlier waves' counts plus the kept lanes below it.  No atomic decides a
-// position: equal inputs give equal lists.
-constexpr uint32_t kSelectBlock = 1024;
-__global__ __launch_bounds__(kSelectBlock) void select_tiles(const double* __restrict__ tile_err,
-                                                                    const uint32_t* __restrict__ in_tiles,
-                                                                    uint32_t n_in, double threshold,
-                                                                    uint32_t* __restrict__ out_tiles,
-                                                                    uint32_t* __restrict__ count) {
-    __shared__ uint32_t wave_n[kSelectBlock / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    uint32_t base = 0;
-    for (uint32_t b0 = 0; b0 < n_in; b0 += kSelectBlock) {  // (n_in <= 2^31: b0 + t does not wrap)
-        const uint32_t j = b0 + t;
-        uint32_t tile = 0;
-        bool keep = false;
-        if (j < n_in) {
-            tile = in_tiles ? in_tiles[j] : j;
-            keep = tile_err[tile] > threshold;  // (a NaN compares false)
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_n[wv] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t pos = base, total = 0;
-        for (uint32_t w = 0; w < kSelectBlock / 64; w++) {
-            const uint32_t n = wave_n[w];
-            pos += w < wv ? n : 0u;
-            total += n;
-        }
-        if (keep) out_tiles[pos + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = tile;
-        base += total;
-        __syncthreads();  // wave_n is rewritten by the next block
-    }
-    if (t == 0) count[0] = base;
-}
-
-// ptmi_trace_multi's device-side combine: out = the partial frames parts[0..nparts)
-// (each npix*4 doubles, RGB sums, A = sample count) summed in part order, times 1/S,
-// alpha 1 (tracer.cl:1184-1187).  out may alias parts[0].
-__global__ __launch_bounds__(256) void combine_kernel(const double* parts, uint32_t nparts, size_t npix,
-                                                      double* out, uint32_t samples) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const size_t stride = npix * 4;
-    double r = parts[4 * i], g = parts[4 * i + 1], b = parts[4 * i + 2];
-    for (uint32_t k = 1; k < nparts; k++) {
-        const double* p = parts + k * stride + 4 * i;
-        r = r + p[0];
-        g = g + p[1];
-        b = b + p[2];
-    }
-    const double w = 1.0 / samples;
-    out[4 * i + 0] = r * w;
-    out[4 * i + 1] = g * w;
-    out[4 * i + 2] = b * w;
-    out[4 * i + 3] = 1.0;
-}
-
-// Seeds with Go rand.Float64 granularity (k / 2^53) from a SplitMix64 stream.
-__global__ __launch_bounds__(256) void seeds_kernel(double* __restrict__ seeds, uint32_t n, uint64_t stream) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t z = stream + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    seeds[i] = (double)(z >> 11) * 0x1p-53;
-}
-
 // ---- host-side launch wrappers (called from ptmi_api.cpp) ----------------------
 int trace_block_threads(int flags) { return kBlock; }
 int trace_tiles_per_block(int flags) { return 1; }
 
-// The instantiation a scene's flags launch: textured and non-affine scenes take the
-// generic ones; F_XRNG exists for the affine instantiations (ptmi_scene_set_rng).
-static int kernel_flags(int flags) {
-    const int mom = flags & F_MOM;  // every instantiation has its moment variant
-    if (flags & F_TEX) return F_ALL | F_PROJ | F_TEX | mom;
-    if (flags & F_PROJ) return F_ALL | F_PROJ | mom;
-    if (flags & F_WIDE) return F_ALL | F_WIDE | (flags & F_XRNG) | mom;
-    if ((flags & F_TLIST) && (flags & F_GROUPS) && !(flags & F_XRNG)) return (flags & (F_ALL | F_TLIST)) | mom;
-    return (flags & (F_ALL | F_XRNG)) | mom;
-}
-
-int trace_kernel_flags(int flags) { return kernel_flags(flags); }
+// The instantiation a launch's flags take (ptmi_flags.h trace_instance_flags) out of the list of
+// those that exist (PTMI_TRACE_INSTANCES, which a static_assert there holds to the mapping).
+int trace_kernel_flags(int flags) { return trace_instance_flags(flags); }
 
 const void* trace_kernel_symbol(int flags) {
-    switch (kernel_flags(flags)) {
+    switch (trace_instance_flags(flags)) {
 #define K(f)                                                          \
     case f: return reinterpret_cast<const void*>(&trace_kernel<f>); \
     case f | F_MOM: return reinterpret_cast<const void*>(&trace_kernel<f | F_MOM>);
-        K(0) K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) K(10) K(11) K(12) K(13) K(14) K(15)
-        K(F_ALL | F_PROJ) K(F_ALL | F_PROJ | F_TEX)
-        K(64) K(65) K(66) K(67) K(68) K(69) K(70) K(71) K(72) K(73) K(74) K(75) K(76) K(77) K(78) K(79)
-        K(129) K(131) K(133) K(135) K(137) K(139) K(141) K(143)
-        K(F_ALL | F_WIDE) K(F_ALL | F_WIDE | F_XRNG)
+        PTMI_TRACE_INSTANCES(K)
 #undef K
     }
     return nullptr;
@@ -3851,7 +3289,7 @@ hipError_t launch_trace(const DevScene& S, int flags, uint32_t samples, const Wo
                         hipStream_t st) {
     const uint32_t items = WP.n_whole + WP.n_tail * WP.nchunks;
     if (items == 0) return hipSuccess;
-    flags = kernel_flags(flags);
+    flags = trace_instance_flags(flags);
     if (((flags & F_MOM) != 0) != (sq != nullptr)) return hipErrorInvalidValue;
     const int threads = trace_block_threads(flags), wpb = trace_tiles_per_block(flags);
     const dim3 grid((items + wpb - 1) / wpb), block(threads);
@@ -3864,11 +3302,7 @@ hipError_t launch_trace(const DevScene& S, int flags, uint32_t samples, const Wo
         hipLaunchKernelGGL(trace_kernel<f | F_MOM>, grid, block, 0, st, S, samples, WP, seeds, sunf, sums, part,    \
                            item_ctr, sq);                                                                           \
         break;
-        K(0) K(1) K(2) K(3) K(4) K(5) K(6) K(7) K(8) K(9) K(10) K(11) K(12) K(13) K(14) K(15)
-        K(F_ALL | F_PROJ) K(F_ALL | F_PROJ | F_TEX)
-        K(64) K(65) K(66) K(67) K(68) K(69) K(70) K(71) K(72) K(73) K(74) K(75) K(76) K(77) K(78) K(79)
-        K(129) K(131) K(133) K(135) K(137) K(139) K(141) K(143)
-        K(F_ALL | F_WIDE) K(F_ALL | F_WIDE | F_XRNG)
+        PTMI_TRACE_INSTANCES(K)
 #undef K
     default:
         return hipErrorInvalidValue;
@@ -3887,55 +3321,10 @@ hipError_t launch_reduce(const double* part, double* sums, const WorkPlan& WP, i
     return hipGetLastError();
 }
 
-// tile_part: 4 doubles per tile of scratch (ptmi_api.cpp ptmi_error_map).
-hipError_t launch_error_map(const double* sums, const double* sq, uint32_t W, uint32_t H, double* se, double* tile_err,
-                            double* tile_part, double* stats, hipStream_t st) {
-    const uint32_t tiles = ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
-    hipLaunchKernelGGL(error_map, dim3(tiles), dim3(64), 0, st, sums, sq, (int)W, (int)H, se, tile_err, tile_part);
-    hipLaunchKernelGGL(error_stats, dim3(1), dim3(256), 0, st, tile_part, tiles, stats);
-    return hipGetLastError();
-}
-
-hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(accumulate_sums, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, src, n);
-    return hipGetLastError();
-}
-
 #if PTMI_STUDY  // the measured tile order (needs PTMI_TILE_COST)
 #define PTMI_STUDY_PART 2
 #include "ptmi_study_kernels.h"
 #endif  // PTMI_STUDY
-
-hipError_t launch_finalize(const double* sums, double* out, uint32_t npix, uint32_t samples, hipStream_t st) {
-    hipLaunchKernelGGL(finalize_kernel, dim3((npix + 255) / 256), dim3(256), 0, st, sums, out, npix, samples);
-    return hipGetLastError();
-}
-
-hipError_t launch_finalize_counts(const double* sums, double* out, uint32_t npix, hipStream_t st) {
-    if (npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(finalize_counts, dim3((npix + 255) / 256), dim3(256), 0, st, sums, out, npix);
-    return hipGetLastError();
-}
-
-hipError_t launch_select_tiles(const double* tile_err, const uint32_t* in_tiles, uint32_t n_in, double threshold,
-                               uint32_t* out_tiles, uint32_t* count, hipStream_t st) {
-    hipLaunchKernelGGL(select_tiles, dim3(1), dim3(kSelectBlock), 0, st, tile_err, in_tiles, n_in, threshold,
-                       out_tiles, count);
-    return hipGetLastError();
-}
-
-hipError_t launch_combine(const double* parts, uint32_t nparts, size_t npix, double* out, uint32_t samples,
-                          hipStream_t st) {
-    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, parts, nparts, npix, out,
-                       samples);
-    return hipGetLastError();
-}
-
-hipError_t launch_seeds(double* seeds, uint32_t n, uint64_t stream, hipStream_t st) {
-    hipLaunchKernelGGL(seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seeds, n, stream);
-    return hipGetLastError();
-}
 
 }  // namespace ptmi
 

@@ -2,7 +2,7 @@
 ptmi_denoise).
 
 ``atrous_reference`` is the numpy restatement of the device filter, operation for operation
-(csrc/ptmi_kernels.hip denoise_start / denoise_pass / denoise_end): the contract's documentation
+(csrc/ptmi_image_kernels.hip denoise_start / denoise_pass / denoise_end): the contract's documentation
 and the comparator of the GPU tests.  Every FP64 operation below is separately rounded and in the
 device's order; ``exp`` is the one operation whose last bits may differ between numpy and the device.
 

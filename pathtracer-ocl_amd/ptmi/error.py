@@ -1,7 +1,7 @@
 """Per-pixel noise estimates from the moment render (ptmi_scene_render_moments, ptmi_error_map).
 
 ``error_map_reference`` is the numpy restatement of the device's error map, operation for
-operation (csrc/ptmi_kernels.hip pixel_err / error_map / error_stats): the formula's
+operation (csrc/ptmi_image_kernels.hip pixel_err / error_map / error_stats): the formula's
 documentation and the comparator of the GPU tests.
 
 ``render_to_noise`` renders a frame batch by batch until its relative noise is below a target.

@@ -2,7 +2,7 @@
 ptmi_reproject): the temporal half of SVGF, in front of the spatial filter of ptmi/denoise.py.
 
 ``reproject_reference`` is the numpy restatement of the device kernel, operation for operation
-(csrc/ptmi_kernels.hip reproject_pass): the contract's documentation and the comparator of the GPU
+(csrc/ptmi_image_kernels.hip reproject_pass): the contract's documentation and the comparator of the GPU
 tests.  Every FP64 operation below is an IEEE add, multiply, divide, square root or floor, separately
 rounded and in the device's order; the world-to-camera matrix is the same cofactor inverse the library
 computes on the host (``cofactor_inverse``).

@@ -17,8 +17,9 @@ if [ "$NAME" = head ] || [ -n "$FROMREV" ]; then
   done
   # (the study kernels' file: revisions before the split keep that code in ptmi_kernels.hip)
   git show $REV:pathtracer-ocl_amd/csrc/ptmi_study_kernels.h > $SRC/ptmi_study_kernels.h 2>/dev/null || rm -f $SRC/ptmi_study_kernels.h
-  # (the tile classifier, the motion records, the flags / launch / plan headers: older revisions have none)
-  for f in ptmi_camcull.h ptmi_motion.h ptmi_flags.h ptmi_launch.h ptmi_plan.h; do
+  # (the tile classifier, the motion records, the flags / launch / plan headers, the image passes' file: older
+  # revisions have none, and keep the image passes in ptmi_kernels.hip)
+  for f in ptmi_camcull.h ptmi_motion.h ptmi_flags.h ptmi_launch.h ptmi_plan.h ptmi_image_kernels.hip; do
     git show $REV:pathtracer-ocl_amd/csrc/$f > $SRC/$f 2>/dev/null || rm -f $SRC/$f
   done
   mkdir -p $(dirname $SRC)/../include
@@ -27,4 +28,5 @@ if [ "$NAME" = head ] || [ -n "$FROMREV" ]; then
   done
 fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -Wno-unused-result \
-  "$@" -shared -o build/exp/libptmi_$NAME.so $SRC/ptmi_kernels.hip $SRC/ptmi_api.cpp $SRC/ptmi_bvh.cpp
+  "$@" -shared -o build/exp/libptmi_$NAME.so $SRC/ptmi_kernels.hip $(ls $SRC/ptmi_image_kernels.hip 2>/dev/null) \
+  $SRC/ptmi_api.cpp $SRC/ptmi_bvh.cpp

@@ -1,14 +1,16 @@
 """DIAGNOSTIC: a fingerprint of the gfx950 ISA of every kernel and out-of-line device function, to
 show that a change elsewhere in the library (another kernel, host code, a refactor) leaves the device
 code as it was.
-    python tools/isa_fingerprint.py [extra hipcc flags ...]
-Compiles csrc/ptmi_kernels.hip to device assembly and prints
+    python tools/isa_fingerprint.py [--csrc DIR] [extra hipcc flags ...]
+Compiles csrc/ptmi_kernels.hip and csrc/ptmi_image_kernels.hip (those of DIR's that exist: a revision from
+before the image passes had a file of their own has the first alone) to device assembly and prints
   - per trace_kernel<FL>: the instruction count, VGPRs, scratch bytes and a hash of the instruction
     stream up to the kernel's first s_endpgm, with labels renumbered in order of appearance (function
     numbering changes when other kernels come or go) -- the format of the committed fingerprint files;
   - then one `fn` line per function in the assembly (the trace kernels again, every other kernel, and
     the out-of-line device functions such as the ocml sin fallback), over the whole function: the same
-    columns, registers and scratch from the function's own info block."""
+    columns, registers and scratch from the function's own info block.  These are sorted by function name,
+    so the listing does not depend on which file holds a function, or where in it."""
 import hashlib
 import os
 import re
@@ -17,14 +19,16 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "pathtracer-ocl_amd", "csrc", "ptmi_kernels.hip")
+CSRC = os.path.join(ROOT, "pathtracer-ocl_amd", "csrc")
+SRCS = ("ptmi_kernels.hip", "ptmi_image_kernels.hip")  # the trace kernels are in the first
 
 
-def device_asm(extra):
+def device_asm(extra, src=os.path.join(CSRC, SRCS[0])):
+    """The device assembly of one file: the trace kernels' by default (tools/isa_moves.py)."""
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-               "-fno-fast-math", "-Wno-unused-result", "--cuda-device-only", "-S", "-o", out, SRC] + list(extra)
+               "-fno-fast-math", "-Wno-unused-result", "--cuda-device-only", "-S", "-o", out, src] + list(extra)
         subprocess.run(cmd, check=True)
         return open(out).read()
 
@@ -79,11 +83,15 @@ def function_fingerprints(asm):
 
 
 if __name__ == "__main__":
-    asm = device_asm(sys.argv[1:])
-    res, meta = fingerprints(asm)
+    args = sys.argv[1:]
+    csrc = CSRC
+    if args[:1] == ["--csrc"]:
+        csrc, args = args[1], args[2:]
+    asms = [device_asm(args, os.path.join(csrc, f)) for f in SRCS if os.path.exists(os.path.join(csrc, f))]
+    res, meta = fingerprints(asms[0])
     for fl in sorted(res):
         n, h, hk = res[fl]
         vg, sc = meta.get(fl, ("?", "?"))
         print("trace_kernel<%-3d> insts %6d  vgpr %-4s scratch %-4s isa %s  isa-ka %s" % (fl, n, vg, sc, h, hk))
-    for name, n, h, hk, vg, sc in function_fingerprints(asm):
+    for name, n, h, hk, vg, sc in sorted(fn for asm in asms for fn in function_fingerprints(asm)):
         print("fn %s insts %6d  vgpr %-4s scratch %-4s isa %s  isa-ka %s" % (name, n, vg, sc, h, hk))
