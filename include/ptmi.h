@@ -344,9 +344,10 @@ int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* fea
  * frames for INDEPENDENT estimates: render them with different seeds.  Two frames with equal seeds and
  * an unchanged camera are the same estimate, and averaging them halves nothing.
  * The guides are the pinhole ray through the pixel centre: the first hit on glass or a mirror
- * reprojects the glass, not what shows through it, and view-dependent shading lags by the history
- * length; the objects are taken to stand still, only the camera moves (ptmi_reproject_motion follows
- * objects that moved); at 1 spp se is +inf and every pixel resets.
+ * reprojects the glass, not what shows through it, and the history is trusted wherever the geometry
+ * matches: view-dependent shading and changed lighting are the business of ptmi_history_gather +
+ * ptmi_rectify, which test the history against the frame; the objects are taken to stand still, only the
+ * camera moves (ptmi_reproject_motion follows objects that moved); at 1 spp se is +inf and every pixel resets.
  * Allocates nothing; asynchronous on the stream.  No output may overlap an input or another output, in
  * whole or in part (callers ping-pong two history buffers; there is no in-place form: out_rgba_dev is
  * not rgba_dev, out_se_dev is not se_dev); the ranges are checked.  Every buffer but se_dev and
@@ -465,7 +466,8 @@ int ptmi_motion_table(const void* prev_objects, const void* cur_objects, uint32_
  *     n' = m / sqrt(l).  x' is projected with the previous camera, and the taps are tested with
  *     n' . n_q >= normal_cos and |n' . (x_q - x')| <= plane_dist * t_p.  The blend is ptmi_reproject's.
  * Rigid and affine motions of whole objects are followed.  Only what the first-hit records carry is:
- * shadows, reflections and indirect light that move with an object lag by the history length, and
+ * for shadows, reflections and indirect light that move with an object see ptmi_rectify (with
+ * ptmi_history_gather in this call's place), and
  * geometry inside a mesh does not deform.  The exact operation order is ptmi/temporal.py
  * reproject_reference with `motion`.  All of ptmi_reproject's rules and argument checks apply; the motion
  * table is one more input no output may overlap, and must be 16-byte aligned.
@@ -476,6 +478,66 @@ int ptmi_reproject_motion(const double* rgba_dev, const double* se_dev, const do
                           double* out_hist_dev, double* out_rgba_dev /* may be NULL */,
                           double* out_se_dev /* may be NULL */, const double* motion_dev, uint32_t n_obj,
                           void* hip_stream, char* err, size_t err_len);
+
+/*
+ * History rectification: ptmi_reproject / ptmi_reproject_motion in two steps, with a test of the history
+ * against this frame between the lookup and the blend.  A history is found by geometry alone, so lighting
+ * that changed (ptmi_scene_set_objects may change emission, colour and material; shadows and reflections
+ * move with an object) would otherwise stay wrong for max_history frames.
+ *
+ * ptmi_history_gather does everything ptmi_reproject (motion_dev == NULL and n_obj == 0) or
+ * ptmi_reproject_motion (a table of n_obj = 1..16 records) does up to the blend, and writes the history as
+ * found: per pixel of gathered_dev (W*H*PTMI_HISTORY_DOUBLES) [0..2] h_c, [3] h_var, [4] h_N, [5..7] 0 --
+ * the very values those calls blend -- and for a pixel they would reset (rgb, se^2, 0): N = 0 says that no
+ * history was found.  Their rules and argument checks apply; max_history is checked and not used.
+ *
+ * ptmi_rectify, per pixel p with colour c_p, v_p = se_p^2, object id id_p and gathered record (h, hv, hn):
+ *   RESET   c_p or se_p not finite: (c_p, v_p, N = 0);  hn == 0: (c_p, v_p, N = 1) -- ptmi_reproject's resets.
+ *   WINDOW  taps q = p + (dx, dy), dy outer, dx inner, both in [-radius, radius], raster order, centre
+ *           included; ACCEPTED when inside the image, id_q == id_p (a NaN id matches nothing), c_q and se_q
+ *           finite and gathered_q.N > 0.  Sequential, separately rounded sums in tap order:
+ *             m += 1;  a_k += c_q.k - c_p.k;  b_k += h_q.k - c_p.k;  sv += se_q^2;  sh += hv_q
+ *   TEST    d_k = (b_k - a_k) / m;  d2 = (d_0^2 + d_1^2) + d_2^2;  V = (sv + sh) / (m m);  T2 = (gamma gamma) V.
+ *           If m >= min_count and d2 > T2:  rho = sqrt(T2 / d2),  f = 1 - rho,  h'_k = h_k - f d_k,
+ *           hn' = rho hn;  otherwise rho = 1 and h' = h, hn' = hn bit for bit (a NaN compares false: not
+ *           rectified).  hv is not changed.
+ *   BLEND   ptmi_reproject's: N' = min(hn' + 1, max_history), a = 1 / N', colour' = h' + a (c_p - h'),
+ *           var' = (a a) v_p + ((1 - a)(1 - a)) hv.
+ *   out_hist_dev = (colour', var', N', rho, 0, 0) ([5] = rho; 1.0 for a reset); out_rgba_dev and
+ *   out_se_dev (each may be NULL) as ptmi_reproject's.  With min_count above (2 radius + 1)^2 the two calls
+ *   give ptmi_reproject's / ptmi_reproject_motion's outputs bit for bit ([5] aside).
+ * The means of the gathered history and of this frame are compared over the same pixels of one object,
+ * against the variance of those two means: what varies inside the window (a penumbra, a texture) is in
+ * both and cancels, a change in time is left, and about 49 pixels give the test 49 times a per-pixel
+ * one's power.  The history is moved by the part of the offset that exceeds the tolerance and its length is
+ * cut by the same factor, so a wrong history is also forgotten sooner.  The exact operation order is
+ * ptmi/temporal.py gather_reference and rectify_reference.
+ * Limits: only a change of the window MEAN is seen; a window with fewer than min_count accepted pixels
+ * (thin objects, object edges) is not tested; the window's pixels are taken for independent, which a
+ * bilinearly gathered history is not -- gamma absorbs that.
+ * Both calls allocate nothing and are asynchronous on the stream.  No output may overlap an input
+ * (gathered_dev is one) or another output; every buffer but se_dev and out_se_dev must be 16-byte aligned.
+ * PTMI_ERR_ARG (no launch, no device call) as ptmi_reproject; for ptmi_history_gather also a motion table
+ * without objects or objects without a table; for ptmi_rectify a radius outside 1..4, a negative or
+ * non-finite gamma, max_history outside 1..65536 and non-zero flags.
+ */
+typedef struct ptmi_rectify_params {
+    uint32_t radius;      /* window half-size, default 3 (7x7); 1..4 */
+    uint32_t min_count;   /* default 9: fewer accepted taps -> no test */
+    double gamma;         /* default 3.0; finite, >= 0 */
+    uint32_t max_history; /* default 32; 1..65536 */
+    uint32_t flags;       /* 0 */
+} ptmi_rectify_params;
+
+int ptmi_history_gather(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                        const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
+                        uint32_t width, uint32_t height, const ptmi_reproject_params* params /* NULL = defaults */,
+                        double* gathered_dev, const double* motion_dev /* NULL: static */, uint32_t n_obj,
+                        void* hip_stream, char* err, size_t err_len);
+int ptmi_rectify(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* gathered_dev,
+                 uint32_t width, uint32_t height, const ptmi_rectify_params* params /* NULL = defaults */,
+                 double* out_hist_dev, double* out_rgba_dev /* may be NULL */, double* out_se_dev /* may be NULL */,
+                 void* hip_stream, char* err, size_t err_len);
 
 /* Kernel timing: with timing enabled, every trace_kernel launch of the scene is
  * bracketed by HIP events recorded on the launch stream; ptmi_scene_kernel_time

@@ -1501,12 +1501,13 @@ static bool cofactor_inverse(const double* m, double* out) {
     return true;
 }
 
-// ptmi_reproject (motion_dev == NULL, n_obj == 0) and ptmi_reproject_motion: one set of checks.
+// ptmi_reproject (motion_dev == NULL, n_obj == 0), ptmi_reproject_motion and ptmi_history_gather (gather:
+// out_hist_dev is the gathered record, and there are no other outputs): one set of checks.
 static int reproject_checked(const double* rgba_dev, const double* se_dev, const double* feat_dev,
                              const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
                              uint32_t width, uint32_t height, const ptmi_reproject_params* params,
                              double* out_hist_dev, double* out_rgba_dev, double* out_se_dev, const double* motion_dev,
-                             uint32_t n_obj, void* hip_stream, char* err, size_t err_len) {
+                             uint32_t n_obj, bool gather, void* hip_stream, char* err, size_t err_len) {
     ptmi_reproject_params p{32, 0, 0.9, 0.02, 0.05};
     if (params) p = *params;
     if (!rgba_dev || !se_dev || !feat_dev || !out_hist_dev || (prev_hist_dev && (!prev_feat_dev || !prev_camera)) ||
@@ -1570,8 +1571,12 @@ static int reproject_checked(const double* rgba_dev, const double* se_dev, const
         a.half_height = cam.half_height;
         a.pixel_size = cam.pixel_size;
     }
-    HIP_TRY(launch_reproject(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev, out_rgba_dev,
-                             out_se_dev, motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
+    if (gather)
+        HIP_TRY(launch_history_gather(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev,
+                                      motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
+    else
+        HIP_TRY(launch_reproject(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev,
+                                 out_rgba_dev, out_se_dev, motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
     return PTMI_OK;
 }
 
@@ -1580,7 +1585,7 @@ int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* f
                    const ptmi_reproject_params* params, double* out_hist_dev, double* out_rgba_dev, double* out_se_dev,
                    void* hip_stream, char* err, size_t err_len) {
     return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
-                             out_hist_dev, out_rgba_dev, out_se_dev, nullptr, 0, hip_stream, err, err_len);
+                             out_hist_dev, out_rgba_dev, out_se_dev, nullptr, 0, false, hip_stream, err, err_len);
 }
 
 int ptmi_reproject_motion(const double* rgba_dev, const double* se_dev, const double* feat_dev,
@@ -1593,7 +1598,71 @@ int ptmi_reproject_motion(const double* rgba_dev, const double* se_dev, const do
         return PTMI_ERR_ARG;
     }
     return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
-                             out_hist_dev, out_rgba_dev, out_se_dev, motion_dev, n_obj, hip_stream, err, err_len);
+                             out_hist_dev, out_rgba_dev, out_se_dev, motion_dev, n_obj, false, hip_stream, err, err_len);
+}
+
+int ptmi_history_gather(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                        const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
+                        uint32_t width, uint32_t height, const ptmi_reproject_params* params, double* gathered_dev,
+                        const double* motion_dev, uint32_t n_obj, void* hip_stream, char* err, size_t err_len) {
+    if ((motion_dev == nullptr) != (n_obj == 0) || n_obj > PTMI_MAX_OBJECTS) {
+        set_err(err, err_len, "bad history_gather arguments (motion table %s, %u objects)", motion_dev ? "given" : "NULL",
+                n_obj);
+        return PTMI_ERR_ARG;
+    }
+    return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
+                             gathered_dev, nullptr, nullptr, motion_dev, n_obj, true, hip_stream, err, err_len);
+}
+
+int ptmi_rectify(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* gathered_dev,
+                 uint32_t width, uint32_t height, const ptmi_rectify_params* params, double* out_hist_dev,
+                 double* out_rgba_dev, double* out_se_dev, void* hip_stream, char* err, size_t err_len) {
+    ptmi_rectify_params p{3, 9, 3.0, 32, 0};
+    if (params) p = *params;
+    if (!rgba_dev || !se_dev || !feat_dev || !gathered_dev || !out_hist_dev || width == 0 || height == 0 ||
+        width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
+        set_err(err, err_len, "bad rectify arguments (%u x %u)", width, height);
+        return PTMI_ERR_ARG;
+    }
+    if (p.radius < 1 || p.radius > 4 || !(std::isfinite(p.gamma) && p.gamma >= 0.0) || p.max_history < 1 ||
+        p.max_history > 65536 || p.flags != 0) {
+        set_err(err, err_len, "bad rectify parameters (radius %u min_count %u gamma %g max_history %u flags %u)", p.radius,
+                p.min_count, p.gamma, p.max_history, p.flags);
+        return PTMI_ERR_ARG;
+    }
+    // No output may overlap an input or another output (the kernel's pointers are __restrict__).
+    const size_t npix = (size_t)width * height;
+    struct Range {
+        const double* p;
+        size_t doubles;
+    };
+    const Range ins[4] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
+                          {gathered_dev, npix * PTMI_HISTORY_DOUBLES}};
+    const Range outs[3] = {{out_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {out_rgba_dev, npix * 4}, {out_se_dev, npix}};
+    auto overlap = [](const Range& a, const Range& b) {
+        if (!a.p || !b.p) return false;
+        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+        return a0 < b0 + b.doubles * sizeof(double) && b0 < a0 + a.doubles * sizeof(double);
+    };
+    bool aliased = false;
+    for (int o = 0; o < 3; o++) {
+        for (int i = 0; i < 4; i++) aliased = aliased || overlap(outs[o], ins[i]);
+        for (int q = o + 1; q < 3; q++) aliased = aliased || overlap(outs[o], outs[q]);
+    }
+    if (aliased || (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)gathered_dev | (uintptr_t)out_hist_dev |
+                     (uintptr_t)out_rgba_dev) & 15u)) {
+        set_err(err, err_len, "rectify buffers overlap or are not 16-byte aligned");
+        return PTMI_ERR_ARG;
+    }
+    RectifyArgs a{};
+    a.W = (int32_t)width;
+    a.H = (int32_t)height;
+    a.min_count = p.min_count;
+    a.gamma2 = p.gamma * p.gamma;
+    a.max_history = (double)p.max_history;
+    HIP_TRY(launch_rectify(rgba_dev, se_dev, feat_dev, gathered_dev, a, p.radius, out_hist_dev, out_rgba_dev, out_se_dev,
+                           (hipStream_t)hip_stream));
+    return PTMI_OK;
 }
 
 int ptmi_scene_set_timing(ptmi_scene* s, int enable) {

@@ -205,6 +205,12 @@ struct ReprojectArgs {
     double half_width, half_height, pixel_size;
     double max_history, normal_cos, plane_dist, min_weight;
 };
+// ptmi_rectify's: the frame, min_count, gamma * gamma (the host's product, as numpy's) and max_history.
+struct RectifyArgs {
+    int32_t W, H;
+    uint32_t min_count, pad;
+    double gamma2, max_history;
+};
 
 // One BVH walk of a ray (walk_kernel / walk_pool_kernel): the world-space ray and the
 // best primitive hit so far (t, pk as Hit::pk), one 64-B line; and its result, the

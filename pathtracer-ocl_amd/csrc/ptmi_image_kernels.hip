@@ -245,7 +245,14 @@ hipError_t launch_denoise(const double* rgba, const double* se, const double* fe
 // one (or an id outside the table) takes the path below with the current point, bit for bit, and an
 // object without a usable motion resets.  The instantiation without kMotion ignores the two trailing
 // arguments and keeps the instruction stream it had as a plain kernel.
-template <bool kMotion>
+//
+// kGather (ptmi_history_gather): the same pass up to the blend, which it leaves to ptmi_rectify -- the
+// record is the history as found, (h_c, h_var, h_N), and a pixel that resets writes (c_p, se_p^2, 0): N = 0
+// says that no history was found.  h_c, h_var and h_N are the values the blend below takes, by the same
+// operations in the same order: one kernel text, and what kGather leaves out is left out at compile time, so
+// the instantiations without it keep the instruction stream they had (tools/isa_fingerprint.py).  It
+// ignores out_rgba and out_se.
+template <bool kMotion, bool kGather>
 __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __restrict__ rgba,
                                                                 const double* __restrict__ se,
                                                                 const double* __restrict__ feat,
@@ -268,7 +275,7 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
     const double v = s * s;
     const bool fin = dn_finite(c0, c1, c2, s);
     // the reset: this frame alone (a pixel that is not finite is no history for the next frame)
-    double o0 = c0, o1 = c1, o2 = c2, ov = v, on = fin ? 1.0 : 0.0;
+    double o0 = c0, o1 = c1, o2 = c2, ov = v, on = kGather ? 0.0 : fin ? 1.0 : 0.0;
     if (prev_hist != nullptr && fin && !(id < 0.0)) {
         // the surface point and its normal as the previous frame saw them
         double ux = px, uy = py, uz = pz, m0 = n0, m1 = n1, m2 = n2;
@@ -338,13 +345,17 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
                 // the history: a constant sequence stays constant bit for bit
                 const double h0 = c0 + r0 / sw, h1 = c1 + r1 / sw, h2 = c2 + r2 / sw;
                 const double hv = sv / (sw * sw), hn = sn / sw;
-                const double np1 = hn + 1.0;
-                on = np1 < a.max_history ? np1 : a.max_history;
-                const double al = 1.0 / on, be = 1.0 - al;
-                o0 = h0 + al * (c0 - h0);
-                o1 = h1 + al * (c1 - h1);
-                o2 = h2 + al * (c2 - h2);
-                ov = (al * al) * v + (be * be) * hv;
+                if constexpr (kGather) {
+                    o0 = h0, o1 = h1, o2 = h2, ov = hv, on = hn;
+                } else {
+                    const double np1 = hn + 1.0;
+                    on = np1 < a.max_history ? np1 : a.max_history;
+                    const double al = 1.0 / on, be = 1.0 - al;
+                    o0 = h0 + al * (c0 - h0);
+                    o1 = h1 + al * (c1 - h1);
+                    o2 = h2 + al * (c2 - h2);
+                    ov = (al * al) * v + (be * be) * hv;
+                }
             }
         }
     }
@@ -352,6 +363,154 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
     oh[0] = make_double2(o0, o1);
     oh[1] = make_double2(o2, ov);
     oh[2] = make_double2(on, 0.0);
+    oh[3] = make_double2(0.0, 0.0);
+    if constexpr (!kGather) {
+        if (out_rgba) {
+            double2* o = reinterpret_cast<double2*>(out_rgba + 4 * i);
+            o[0] = make_double2(o0, o1);
+            o[1] = make_double2(o2, 1.0);
+        }
+        if (out_se) out_se[i] = sqrt(ov);
+    }
+}
+
+hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
+                            const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
+                            double* out_se, const double* motion, int32_t n_obj, hipStream_t st) {
+    const dim3 grid(((uint32_t)a.W + kDnX - 1) / kDnX, ((uint32_t)a.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
+    if (motion)
+        hipLaunchKernelGGL((reproject_pass<true, false>), grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
+                           out_rgba, out_se, motion, (int)n_obj);
+    else
+        hipLaunchKernelGGL((reproject_pass<false, false>), grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
+                           out_rgba, out_se, motion, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_history_gather(const double* rgba, const double* se, const double* feat, const double* prev_hist,
+                                 const double* prev_feat, const ReprojectArgs& a, double* gathered,
+                                 const double* motion, int32_t n_obj, hipStream_t st) {
+    const dim3 grid(((uint32_t)a.W + kDnX - 1) / kDnX, ((uint32_t)a.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
+    if (motion)
+        hipLaunchKernelGGL((reproject_pass<true, true>), grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a,
+                           gathered, nullptr, nullptr, motion, (int)n_obj);
+    else
+        hipLaunchKernelGGL((reproject_pass<false, true>), grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a,
+                           gathered, nullptr, nullptr, motion, 0);
+    return hipGetLastError();
+}
+
+// ---- History rectification (ptmi_rectify) ------------------------------------------------------
+// The gathered history (ptmi_history_gather) tested against this frame over a (2 kR + 1)^2 window of
+// pixels on the same object, corrected by the offset found, and blended as reproject_pass blends.  Every
+// FP64 operation is separately rounded and in the order ptmi/temporal.py rectify_reference states.
+//
+// One thread per pixel on the 16 x 16 blocks.  The block and its halo of kR are staged in LDS as ten
+// planes of doubles -- colour x 3, se^2, h x 3, h_var, N, id -- and each thread walks its taps from there
+// (a global gather would read 49 x 80 B per pixel at kR = 3).  N is staged as 0 for an entry outside the
+// image or whose colour or se is not finite: a tap is accepted on N > 0 and an equal id alone, and of an
+// entry outside the image nothing else is written or used.
+//
+// Layout: rows of kRcPitch = 24 doubles in every plane, whatever kR (16 + 2 kR <= 24).  ds_read_b64 banks
+// by (address / 4) mod 64 -- 32 doubles -- within each 32-lane half of a wave, and a half reads two rows of
+// 16 consecutive doubles.  The four rows of a wave go to its 16-lane groups in the order 0, 2, 1, 3, so a
+// half's rows are two apart: 48 doubles = 16 mod 32, the two runs of 16 fill the 32 banks once, and no
+// tap read conflicts at any kR or tap offset (adjacent rows, 24 apart, would share 8 banks).  At kR = 4
+// the planes are 24 x 24 x 10 x 8 B = 46 KB, three blocks per CU; at kR = 1, 34.6 KB.
+struct RcPlane {
+    enum { c0, c1, c2, v, h0, h1, h2, hv, n, id, count };
+};
+static constexpr int kRcPitch = 24;
+template <int kR>
+__global__ __launch_bounds__(kDnX * kDnY) void rectify_pass(const double* __restrict__ rgba,
+                                                              const double* __restrict__ se,
+                                                              const double* __restrict__ feat,
+                                                              const double* __restrict__ gathered, RectifyArgs a,
+                                                              double* __restrict__ out_hist,
+                                                              double* __restrict__ out_rgba,
+                                                              double* __restrict__ out_se) {
+    constexpr int kTW = kDnX + 2 * kR, kTH = kDnY + 2 * kR;
+    static_assert(kTW <= kRcPitch, "a tile row fits the pitch");
+    __shared__ double lds[RcPlane::count][kTH * kRcPitch];
+    const int W = a.W, H = a.H;
+    const int bx0 = (int)blockIdx.x * kDnX, by0 = (int)blockIdx.y * kDnY;
+    for (int k = (int)threadIdx.x; k < kTW * kTH; k += kDnX * kDnY) {
+        const int tx = k % kTW, ty = k / kTW, e = ty * kRcPitch + tx;
+        const int qx = bx0 - kR + tx, qy = by0 - kR + ty;
+        if (qx < 0 || qx >= W || qy < 0 || qy >= H) {
+            lds[RcPlane::n][e] = 0.0;
+            continue;
+        }
+        const size_t q = (size_t)qy * W + qx;
+        const double2* p = reinterpret_cast<const double2*>(rgba + 4 * q);
+        const double2* g = reinterpret_cast<const double2*>(gathered + 8 * q);
+        const double2 p0 = p[0], p1 = p[1], g0 = g[0], g1 = g[1], g2 = g[2];
+        const double s = se[q];
+        lds[RcPlane::c0][e] = p0.x, lds[RcPlane::c1][e] = p0.y, lds[RcPlane::c2][e] = p1.x, lds[RcPlane::v][e] = s * s;
+        lds[RcPlane::h0][e] = g0.x, lds[RcPlane::h1][e] = g0.y, lds[RcPlane::h2][e] = g1.x, lds[RcPlane::hv][e] = g1.y;
+        lds[RcPlane::n][e] = dn_finite(p0.x, p0.y, p1.x, s) ? g2.x : 0.0;
+        lds[RcPlane::id][e] = feat[12 * q + 7];
+    }
+    __syncthreads();
+    // rows 0, 2, 1, 3 of the wave's four to its 16-lane groups (the layout note above)
+    const int lane = (int)threadIdx.x & 63, grp = lane >> 4;
+    const int lx = lane & 15, ly = ((int)threadIdx.x >> 6) * 4 + (((grp & 1) << 1) | (grp >> 1));
+    const int x = bx0 + lx, y = by0 + ly;
+    if (x >= W || y >= H) return;
+    const size_t i = (size_t)y * W + x;
+    const int ce = (ly + kR) * kRcPitch + (lx + kR);
+    const double c0 = lds[RcPlane::c0][ce], c1 = lds[RcPlane::c1][ce], c2 = lds[RcPlane::c2][ce];
+    const double v = lds[RcPlane::v][ce], idp = lds[RcPlane::id][ce];
+    const double hv = lds[RcPlane::hv][ce], hn = lds[RcPlane::n][ce];  // (hn: 0 where the pixel is not finite)
+    const bool fin = dn_finite(c0, c1, c2, se[i]);
+    // the resets: this frame alone
+    double o0 = c0, o1 = c1, o2 = c2, ov = v, on = fin ? 1.0 : 0.0, rho = 1.0;
+    if (fin && hn != 0.0) {
+        uint32_t m = 0;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, sv = 0.0, sh = 0.0;
+        for (int dy = -kR; dy <= kR; dy++) {
+#pragma unroll
+            for (int dx = -kR; dx <= kR; dx++) {
+                const int e = ce + dy * kRcPitch + dx;
+                if (!(lds[RcPlane::n][e] > 0.0) || lds[RcPlane::id][e] != idp) continue;  // (a NaN id matches nothing)
+                m = m + 1;
+                a0 = a0 + (lds[RcPlane::c0][e] - c0);
+                a1 = a1 + (lds[RcPlane::c1][e] - c1);
+                a2 = a2 + (lds[RcPlane::c2][e] - c2);
+                b0 = b0 + (lds[RcPlane::h0][e] - c0);
+                b1 = b1 + (lds[RcPlane::h1][e] - c1);
+                b2 = b2 + (lds[RcPlane::h2][e] - c2);
+                sv = sv + lds[RcPlane::v][e];
+                sh = sh + lds[RcPlane::hv][e];
+            }
+        }
+        double h0 = lds[RcPlane::h0][ce], h1 = lds[RcPlane::h1][ce], h2 = lds[RcPlane::h2][ce], hr = hn;
+        if (m >= a.min_count) {
+            const double md = (double)m;
+            const double d0 = (b0 - a0) / md, d1 = (b1 - a1) / md, d2 = (b2 - a2) / md;
+            const double dd = (d0 * d0 + d1 * d1) + d2 * d2;
+            const double t2 = a.gamma2 * ((sv + sh) / (md * md));
+            if (dd > t2) {  // (a NaN on either side: not rectified)
+                rho = sqrt(t2 / dd);
+                const double f = 1.0 - rho;
+                h0 = h0 - f * d0;
+                h1 = h1 - f * d1;
+                h2 = h2 - f * d2;
+                hr = rho * hn;
+            }
+        }
+        const double np1 = hr + 1.0;
+        on = np1 < a.max_history ? np1 : a.max_history;
+        const double al = 1.0 / on, be = 1.0 - al;
+        o0 = h0 + al * (c0 - h0);
+        o1 = h1 + al * (c1 - h1);
+        o2 = h2 + al * (c2 - h2);
+        ov = (al * al) * v + (be * be) * hv;
+    }
+    double2* oh = reinterpret_cast<double2*>(out_hist + 8 * i);
+    oh[0] = make_double2(o0, o1);
+    oh[1] = make_double2(o2, ov);
+    oh[2] = make_double2(on, rho);
     oh[3] = make_double2(0.0, 0.0);
     if (out_rgba) {
         double2* o = reinterpret_cast<double2*>(out_rgba + 4 * i);
@@ -361,16 +520,17 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
     if (out_se) out_se[i] = sqrt(ov);
 }
 
-hipError_t launch_reproject(const double* rgba, const double* se, const double* feat, const double* prev_hist,
-                            const double* prev_feat, const ReprojectArgs& a, double* out_hist, double* out_rgba,
-                            double* out_se, const double* motion, int32_t n_obj, hipStream_t st) {
+hipError_t launch_rectify(const double* rgba, const double* se, const double* feat, const double* gathered,
+                          const RectifyArgs& a, uint32_t radius, double* out_hist, double* out_rgba, double* out_se,
+                          hipStream_t st) {
     const dim3 grid(((uint32_t)a.W + kDnX - 1) / kDnX, ((uint32_t)a.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
-    if (motion)
-        hipLaunchKernelGGL(reproject_pass<true>, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
-                           out_rgba, out_se, motion, (int)n_obj);
-    else
-        hipLaunchKernelGGL(reproject_pass<false>, grid, block, 0, st, rgba, se, feat, prev_hist, prev_feat, a, out_hist,
-                           out_rgba, out_se, motion, 0);
+    switch (radius) {
+        case 1: hipLaunchKernelGGL(rectify_pass<1>, grid, block, 0, st, rgba, se, feat, gathered, a, out_hist, out_rgba, out_se); break;
+        case 2: hipLaunchKernelGGL(rectify_pass<2>, grid, block, 0, st, rgba, se, feat, gathered, a, out_hist, out_rgba, out_se); break;
+        case 3: hipLaunchKernelGGL(rectify_pass<3>, grid, block, 0, st, rgba, se, feat, gathered, a, out_hist, out_rgba, out_se); break;
+        case 4: hipLaunchKernelGGL(rectify_pass<4>, grid, block, 0, st, rgba, se, feat, gathered, a, out_hist, out_rgba, out_se); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -35,7 +35,10 @@
 // the accumulated frame.  --move-object I --move-step DX,DY,DZ moves object I of the scene's list along the
 // sequence (ptmi_scene_set_objects): in frame k it carries translate(k * step) * transform with the inverse and
 // inverse transpose of that product (ptmi/temporal.py move_object), and --temporal then follows it
-// (ptmi_motion_table, ptmi_reproject_motion).
+// (ptmi_motion_table, ptmi_reproject_motion).  --rectify (with --temporal) tests the history against each
+// frame before it is blended (ptmi_history_gather, ptmi_rectify; --rectify-gamma G, default 3, and
+// --rectify-radius R, 1..4, default 3), and --emission-step F multiplies the emission of every emissive object
+// by F from frame N / 2 on (ptmi_scene_set_objects): a lighting change from the command line.
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
 #include <algorithm>
 #include <chrono>
@@ -77,6 +80,9 @@ struct Cfg {
     int move_object = -1;
     bool have_move = false, have_move_step = false;
     double move_step[3] = {0.0, 0.0, 0.0};
+    bool rectify = false, have_gamma = false, have_radius = false, have_emission = false;
+    double rectify_gamma = 3.0, emission_step = 1.0;
+    int rectify_radius = 3;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -87,7 +93,8 @@ struct Cfg {
                  "          [--seed N] [--noise-target X] [--batch N] [--error-map FILE.raw]\n"
                  "          [--adaptive] [--sample-map FILE.raw] [--denoise] [--denoise-iters N]\n"
                  "          [--features FILE.raw] [--frames N] [--orbit-step DEGREES] [--temporal] [--max-history N]\n"
-                 "          [--move-object I --move-step DX,DY,DZ]\n",
+                 "          [--move-object I --move-step DX,DY,DZ] [--rectify] [--rectify-gamma G] [--rectify-radius R]\n"
+                 "          [--emission-step F]\n",
                  msg);
     std::exit(2);
 }
@@ -141,6 +148,10 @@ Cfg parse(int argc, char** argv) {
             c.have_move_step = true;
         }
         else if (a == "--max-history") c.max_history = std::atoi(val().c_str());
+        else if (a == "--rectify") c.rectify = true;
+        else if (a == "--rectify-gamma") c.rectify_gamma = std::atof(val().c_str()), c.have_gamma = true;
+        else if (a == "--rectify-radius") c.rectify_radius = std::atoi(val().c_str()), c.have_radius = true;
+        else if (a == "--emission-step") c.emission_step = std::atof(val().c_str()), c.have_emission = true;
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
@@ -169,6 +180,12 @@ Cfg parse(int argc, char** argv) {
     if (c.max_history && !c.temporal) usage("--max-history needs --temporal");
     if (c.temporal && c.max_history && (c.max_history < 1 || c.max_history > 65536)) usage("--max-history must be 1..65536");
     if (c.max_history < 0) usage("--max-history must be 1..65536");
+    if (c.rectify && !c.temporal) usage("--rectify needs --temporal");
+    if ((c.have_gamma || c.have_radius) && !c.rectify) usage("--rectify-gamma and --rectify-radius need --rectify");
+    if (c.have_gamma && !(std::isfinite(c.rectify_gamma) && c.rectify_gamma >= 0.0)) usage("--rectify-gamma must be finite and >= 0");
+    if (c.have_radius && (c.rectify_radius < 1 || c.rectify_radius > 4)) usage("--rectify-radius must be 1..4");
+    if (c.have_emission && !sequence) usage("--emission-step needs --frames N with N > 1");
+    if (c.have_emission && !(std::isfinite(c.emission_step) && c.emission_step >= 0.0)) usage("--emission-step must be finite and >= 0");
     if (c.temporal && c.samples < 2) usage("--temporal needs --samples >= 2 (the variance of a frame)");
     if (c.batch <= 0 || (c.have_target && !(c.noise_target >= 0.0))) usage("--batch must be positive, --noise-target >= 0");
     return c;
@@ -346,7 +363,8 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
                                         r.camera, tex, &sc, err, err_len);
     if (rc) return rc;
     double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *se = nullptr, *stats = nullptr, *image = nullptr,
-           *acc = nullptr, *acc_se = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr, *motion = nullptr;
+           *acc = nullptr, *acc_se = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr, *motion = nullptr,
+           *gathered = nullptr;
     double *feat[2] = {nullptr, nullptr}, *hist[2] = {nullptr, nullptr};
     auto hip = [&](hipError_t e, const char* what) {
         if (e == hipSuccess) return false;
@@ -367,9 +385,9 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
     const size_t obj_bytes = (size_t)r.n_obj * PTMI_OBJECT_BYTES;
     std::vector<unsigned char> objs, prev_objs;
     ptmi_host::Mat transform0 = ptmi_host::identity();
-    if (moving) {
+    if (moving || c.have_emission) {
         objs.assign((const unsigned char*)r.objects, (const unsigned char*)r.objects + obj_bytes);
-        std::memcpy(transform0.data(), objs.data() + (size_t)c.move_object * PTMI_OBJECT_BYTES, sizeof(double) * 16);
+        if (moving) std::memcpy(transform0.data(), objs.data() + (size_t)c.move_object * PTMI_OBJECT_BYTES, sizeof(double) * 16);
     }
     do {
         if (hip(hipSetDevice(c.device_index), "hipSetDevice")) break;
@@ -383,6 +401,7 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
         if (c.denoise && (dmalloc(&dn_out, n * 4) || dmalloc(&dn_se, n) || hip(hipMalloc((void**)&dn_work, wb), "hipMalloc")))
             break;
         if (moving && c.temporal && dmalloc(&motion, (size_t)PTMI_MOTION_DOUBLES * PTMI_MAX_OBJECTS)) break;
+        if (c.rectify && dmalloc(&gathered, n * PTMI_HISTORY_DOUBLES)) break;
         for (int k = 0; k < c.frames && !rc; k++) {
             if (moving) {
                 prev_objs = objs;
@@ -394,8 +413,18 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
                 std::memcpy(o, t.data(), 128);  // CLObject.transform, inverse, inverseTranspose (ocltracer.go:25-28)
                 std::memcpy(o + 128, ti.data(), 128);
                 std::memcpy(o + 256, tit.data(), 128);
-                if ((rc = ptmi_scene_set_objects(sc, objs.data(), r.n_obj, err, err_len))) break;
             }
+            const bool dim = c.have_emission && k == c.frames / 2;
+            if (dim) {  // CLObject.emission (ocltracer.go:25-28): rgb of every object, times F (0 stays 0)
+                for (uint32_t j = 0; j < r.n_obj; j++) {
+                    double e[3];
+                    unsigned char* o = objs.data() + (size_t)j * PTMI_OBJECT_BYTES + 416;
+                    std::memcpy(e, o, sizeof(e));
+                    for (double& v : e) v = v * c.emission_step;
+                    std::memcpy(o, e, sizeof(e));
+                }
+            }
+            if ((moving || dim) && (rc = ptmi_scene_set_objects(sc, objs.data(), r.n_obj, err, err_len))) break;
             std::memcpy(cam, cam0, sizeof(cam));
             const ptmi_host::Mat rot = ptmi_host::rotate_y(((double)k * c.orbit_step) * M_PI / 180.0);
             const ptmi_host::Mat inv = ptmi_host::multiply(rot, inv0);
@@ -412,8 +441,16 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             if (c.temporal) {
                 ptmi_reproject_params rp{32, 0, 0.9, 0.02, 0.05};
                 if (c.max_history) rp.max_history = (uint32_t)c.max_history;
-                if (moving && k) {
-                    if ((rc = ptmi_motion_table(prev_objs.data(), objs.data(), r.n_obj, motion, nullptr, err, err_len))) break;
+                if (moving && k && (rc = ptmi_motion_table(prev_objs.data(), objs.data(), r.n_obj, motion, nullptr, err, err_len)))
+                    break;
+                if (c.rectify) {
+                    ptmi_rectify_params tp{(uint32_t)c.rectify_radius, 9, c.rectify_gamma, rp.max_history, 0};
+                    if ((rc = ptmi_history_gather(image, se, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
+                                                  k ? prev_cam : nullptr, W, H, &rp, gathered, moving && k ? motion : nullptr,
+                                                  moving && k ? r.n_obj : 0, nullptr, err, err_len)))
+                        break;
+                    rc = ptmi_rectify(image, se, f, gathered, W, H, &tp, hist[k & 1], acc, acc_se, nullptr, err, err_len);
+                } else if (moving && k) {
                     rc = ptmi_reproject_motion(image, se, f, hist[(k - 1) & 1], feat[(k - 1) & 1], prev_cam, W, H, &rp,
                                                hist[k & 1], acc, acc_se, motion, r.n_obj, nullptr, err, err_len);
                 } else {
@@ -438,7 +475,7 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             std::fprintf(stderr, "frame %d (%.6g degrees): wrote %s\n", k, (double)k * c.orbit_step, name.c_str());
         }
     } while (false);
-    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, motion, feat[0], feat[1],
+    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, motion, gathered, feat[0], feat[1],
                       hist[0], hist[1]})
         if (p) (void)hipFree(p);
     ptmi_scene_destroy(sc);

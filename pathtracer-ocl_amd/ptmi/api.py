@@ -40,7 +40,8 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_scene_set_rng", "ptmi_index_stats", "ptmi_scene_render_moments", "ptmi_error_map", "ptmi_accumulate",
            "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts", "ptmi_scene_features",
            "ptmi_denoise", "ptmi_denoise_work_bytes", "ptmi_scene_set_camera", "ptmi_reproject",
-           "ptmi_scene_set_objects", "ptmi_motion_table", "ptmi_reproject_motion")
+           "ptmi_scene_set_objects", "ptmi_motion_table", "ptmi_reproject_motion", "ptmi_history_gather",
+           "ptmi_rectify")
 FEATURE_DOUBLES = 12    # PTMI_FEATURE_DOUBLES: doubles per pixel of Scene.features
 HISTORY_DOUBLES = 8     # PTMI_HISTORY_DOUBLES: doubles per pixel of a reproject history
 MOTION_DOUBLES = 24     # PTMI_MOTION_DOUBLES: doubles per object of a motion table
@@ -72,6 +73,15 @@ class ReprojectParams(ctypes.Structure):
 
     def __init__(self, max_history=32, flags=0, normal_cos=0.9, plane_dist=0.02, min_weight=0.05):
         super().__init__(max_history, flags, normal_cos, plane_dist, min_weight)
+
+
+class RectifyParams(ctypes.Structure):
+    """ptmi_rectify_params (include/ptmi.h); the constructor's defaults are the library's."""
+    _fields_ = [("radius", ctypes.c_uint32), ("min_count", ctypes.c_uint32), ("gamma", ctypes.c_double),
+                ("max_history", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+    def __init__(self, radius=3, min_count=9, gamma=3.0, max_history=32, flags=0):
+        super().__init__(radius, min_count, gamma, max_history, flags)
 
 
 class PtmiError(RuntimeError):
@@ -157,6 +167,12 @@ def load_library(path=None):
         lib.ptmi_reproject_motion.restype = i32
         lib.ptmi_reproject_motion.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(ReprojectParams), vp, vp,
                                               vp, vp, u32, vp, cp, sz]
+    if hasattr(lib, "ptmi_rectify"):  # (likewise)
+        lib.ptmi_history_gather.restype = i32
+        lib.ptmi_history_gather.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(ReprojectParams), vp, vp,
+                                            u32, vp, cp, sz]
+        lib.ptmi_rectify.restype = i32
+        lib.ptmi_rectify.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(RectifyParams), vp, vp, vp, vp, cp, sz]
     if hasattr(lib, "ptmi_diag_scene_tile_cost"):
         lib.ptmi_diag_scene_tile_cost.restype = i32
         lib.ptmi_diag_scene_tile_cost.argtypes = [vp, vp, u32, cp, sz]
@@ -689,3 +705,52 @@ def reproject_motion(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, p
         ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_hist_ptr or None),
         ctypes.c_void_p(out_rgba_ptr or None), ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(motion_ptr or None),
         int(n_obj), ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def _camera_record(prev_camera):
+    if prev_camera is None:
+        return None
+    cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
+    if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
+        raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
+                                                                           cam.dtype.itemsize))
+    return cam
+
+
+def history_gather(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_camera, w, h, gathered_ptr,
+                   motion_ptr=0, n_obj=0, params=None, stream=0):
+    """ptmi_history_gather: reproject() -- or, with motion_ptr and n_obj, reproject_motion() -- up to the
+    blend: gathered_ptr (W*H*HISTORY_DOUBLES) gets per pixel the history as found, (h_c, h_var, h_N, 0...),
+    and (rgb, se^2, N = 0) where those calls would reset.  rectify() tests and blends it.  The operation
+    order is ptmi/temporal.py gather_reference."""
+    p = reproject_params(params)
+    cam = _camera_record(prev_camera)
+    err = ctypes.create_string_buffer(512)
+    _check(load_library().ptmi_history_gather(
+        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
+        ctypes.c_void_p(prev_hist_ptr or None), ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
+        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(gathered_ptr or None),
+        ctypes.c_void_p(motion_ptr or None), int(n_obj), ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def rectify_params(params=None):
+    """A RectifyParams from None (the defaults), a RectifyParams or a dict of some of its fields."""
+    if params is None or isinstance(params, RectifyParams):
+        return params
+    return RectifyParams(**dict(params))
+
+
+def rectify(rgba_ptr, se_ptr, feat_ptr, gathered_ptr, w, h, out_hist_ptr, out_rgba_ptr=0, out_se_ptr=0, params=None,
+            stream=0):
+    """ptmi_rectify: the gathered history (history_gather) tested against this frame over a window of
+    pixels on the same object, corrected by the offset found and blended as reproject() blends.
+    out_hist_ptr gets (colour', var', N', rho, 0, 0) per pixel; out_rgba_ptr / out_se_ptr (optional) the
+    accumulated frame and its standard error.  params: None, a RectifyParams or a dict of its fields.  The
+    operation order is ptmi/temporal.py rectify_reference."""
+    p = rectify_params(params)
+    err = ctypes.create_string_buffer(512)
+    _check(load_library().ptmi_rectify(
+        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
+        ctypes.c_void_p(gathered_ptr or None), int(w), int(h), ctypes.byref(p) if p is not None else None,
+        ctypes.c_void_p(out_hist_ptr or None), ctypes.c_void_p(out_rgba_ptr or None),
+        ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(stream), err, len(err)), err)

@@ -17,7 +17,11 @@ length.  Objects may move between frames (Scene.set_objects, ``move_object``): `
 the `motion` argument of ``reproject_reference`` restate ptmi_motion_table and ptmi_reproject_motion, which
 carry each first hit back to where that surface point was.  Only what the first-hit records carry is
 followed: shadows, reflections and indirect light that move with an object lag by the history length, and
-geometry inside a mesh does not deform.  The variance needs at least 2 spp per frame (at
+geometry inside a mesh does not deform.  ``gather_reference`` and ``rectify_reference`` restate
+ptmi_history_gather and ptmi_rectify (``render_sequence(rectify=...)``), which test the history found
+against the frame over a window of same-object pixels and so bound that lag; they see a change of the
+window's mean only, test no window of fewer than min_count such pixels, and take the window's pixels for
+independent.  The variance needs at least 2 spp per frame (at
 1 spp the standard error is +inf and every pixel resets), and it takes the frames for independent
 estimates: render them with different seeds.  One GPU.
 """
@@ -159,6 +163,21 @@ def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h,
 
     var' is the variance of the blend when the frames are independent estimates (different seeds).
     details=True also returns a dict of the decisions' test quantities (``undecided``)."""
+    return _reproject(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params, details, motion, n_obj, False)
+
+
+def gather_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params=None, details=False, motion=None,
+                     n_obj=0):
+    """gathered[W*H*8]: the device kernel ptmi_history_gather, restated: everything ``reproject_reference``
+    does up to the blend (one body, ``_reproject``), and per pixel the history as found -- (h_c, h_var, h_N,
+    0, 0, 0), the very values that function blends -- or, where it RESETS, (c_p, v_p, N = 0): N = 0 says
+    that no history was found.  `motion`, `n_obj` and details=True (then (gathered, info)) as there."""
+    res = _reproject(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params, details, motion, n_obj, True)
+    return (res[0], res[3]) if details else res[0]
+
+
+def _reproject(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params, details, motion, n_obj, gather):
+    """The body of reproject_reference (gather=False) and gather_reference (gather=True)."""
     p = params_dict(params)
     w, h = int(w), int(h)
     rgba = np.asarray(rgba, dtype=np.float64).reshape(h, w, 4)
@@ -168,7 +187,7 @@ def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h,
     with np.errstate(all="ignore"):
         v = se * se
         fin = np.isfinite(c).all(-1) & np.isfinite(se)
-        out_c, out_v, out_n = c.copy(), v.copy(), np.where(fin, 1.0, 0.0)
+        out_c, out_v, out_n = c.copy(), v.copy(), np.zeros((h, w)) if gather else np.where(fin, 1.0, 0.0)
         info = dict(candidate=np.zeros((h, w), dtype=bool))
         if prev_hist is not None:
             ph = np.asarray(prev_hist, dtype=np.float64).reshape(h * w, HISTORY_DOUBLES)
@@ -232,6 +251,8 @@ def reproject_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h,
             b = 1.0 - a
             c_new = h_c + a[..., None] * (c - h_c)
             v_new = (a * a) * v + (b * b) * h_v
+            if gather:  # the history as found
+                c_new, v_new, n_new = h_c, h_v, h_n
             out_c = np.where(blend[..., None], c_new, out_c)
             out_v = np.where(blend, v_new, out_v)
             out_n = np.where(blend, n_new, out_n)
@@ -270,6 +291,105 @@ def undecided(info, w, h, params=None, rtol=1e-9):
     return out
 
 
+RECTIFY_DEFAULTS = dict(radius=3, min_count=9, gamma=3.0, max_history=32, flags=0)
+H_RHO = 5  # a rectified history's [5]: rho
+
+
+def rectify_params_dict(params=None):
+    """The parameters as a dict with the defaults filled in (ptmi_rectify_params): from None, True, a dict
+    of some fields, or an object with those attributes (api.RectifyParams)."""
+    p = dict(RECTIFY_DEFAULTS)
+    if params is not None and params is not True:
+        for k in p:
+            if isinstance(params, dict):
+                if k in params:
+                    p[k] = params[k]
+            elif hasattr(params, k):
+                p[k] = getattr(params, k)
+    for k in ("radius", "min_count", "max_history", "flags"):
+        p[k] = int(p[k])
+    p["gamma"] = float(p["gamma"])
+    if not (1 <= p["radius"] <= 4 and 0 <= p["min_count"] < 2 ** 32 and np.isfinite(p["gamma"]) and p["gamma"] >= 0.0 and
+            1 <= p["max_history"] <= 65536 and p["flags"] == 0):
+        raise ValueError("bad rectify parameters %r" % (p,))
+    return p
+
+
+def rectify_reference(rgba, se, feat, gathered, w, h, params=None, details=False):
+    """(hist[W*H*8], out_rgba[W*H*4], out_se[W*H]): the device kernel ptmi_rectify, restated.
+
+    Per pixel p with c_p = rgba[p][:3], v_p = se_p * se_p, id_p = feat[p][7] and gathered record
+    (h, hv, hn) (``gather_reference``):
+      RESET   c_p or se_p not finite: (c_p, v_p, N = 0);  hn == 0: (c_p, v_p, N = 1); rho = 1.
+      WINDOW  taps q = p + (dx, dy), dy outer, dx inner, both in [-radius, radius]; ACCEPTED when inside the
+              image, id_q == id_p (a NaN id matches nothing), c_q and se_q finite, gathered_q.N > 0; in tap
+              order   m += 1;  a_k += c_q.k - c_p.k;  b_k += h_q.k - c_p.k;  sv += v_q;  sh += hv_q
+      TEST    d_k = (b_k - a_k) / m;  d2 = (d_0 d_0 + d_1 d_1) + d_2 d_2;  V = (sv + sh) / (m m);
+              T2 = (gamma gamma) V.  If m >= min_count and d2 > T2:
+                rho = sqrt(T2 / d2);  f = 1 - rho;  h'_k = h_k - f d_k;  hn' = rho hn
+              else rho = 1, h' = h, hn' = hn (bit for bit; a NaN compares false).  hv stays.
+      BLEND   N' = min(hn' + 1, max_history);  a = 1 / N';  b = 1 - a;  c' = h' + a (c_p - h');
+              var' = (a a) v_p + (b b) hv       -- reproject_reference's, in its operations and order.
+    out_hist = (c', var', N', rho, 0, 0);  out_rgba = (c', 1.0);  out_se = sqrt(var').
+    details=True also returns dict(m=, d2=, T2=, rho=) as [H, W] arrays."""
+    p = rectify_params_dict(params)
+    w, h, r = int(w), int(h), p["radius"]
+    rgba = np.asarray(rgba, dtype=np.float64).reshape(h, w, 4)
+    se = np.asarray(se, dtype=np.float64).reshape(h, w)
+    oid = np.asarray(feat, dtype=np.float64).reshape(h, w, FEATURE_DOUBLES)[..., F_ID]
+    g = np.asarray(gathered, dtype=np.float64).reshape(h, w, HISTORY_DOUBLES)
+    c, hc, hv, hn = rgba[..., :3], g[..., H_COL], g[..., H_VAR], g[..., H_N]
+    with np.errstate(all="ignore"):
+        v = se * se
+        fin = np.isfinite(c).all(-1) & np.isfinite(se)
+        usable = fin & (hn > 0.0)
+
+        def shifted(a, dx, dy, fill):
+            """a[y + dy, x + dx], `fill` outside the image."""
+            out = np.full(a.shape, fill, dtype=a.dtype)
+            ys, yd = slice(max(dy, 0), h + min(dy, 0)), slice(max(-dy, 0), h + min(-dy, 0))
+            xs, xd = slice(max(dx, 0), w + min(dx, 0)), slice(max(-dx, 0), w + min(-dx, 0))
+            out[yd, xd] = a[ys, xs]
+            return out
+
+        m = np.zeros((h, w), dtype=np.int64)
+        sa, sb, sv, sh = np.zeros((h, w, 3)), np.zeros((h, w, 3)), np.zeros((h, w)), np.zeros((h, w))
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                ok = shifted(usable, dx, dy, False) & (shifted(oid, dx, dy, np.nan) == oid)
+                m = np.where(ok, m + 1, m)
+                sa = np.where(ok[..., None], sa + (shifted(c, dx, dy, 0.0) - c), sa)
+                sb = np.where(ok[..., None], sb + (shifted(hc, dx, dy, 0.0) - c), sb)
+                sv = np.where(ok, sv + shifted(v, dx, dy, 0.0), sv)
+                sh = np.where(ok, sh + shifted(hv, dx, dy, 0.0), sh)
+        md = m.astype(np.float64)
+        d = (sb - sa) / md[..., None]
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        t2 = (p["gamma"] * p["gamma"]) * ((sv + sh) / (md * md))
+        blend = fin & (hn != 0.0)
+        rect = blend & (m >= p["min_count"]) & (d2 > t2)
+        rho = np.where(rect, np.sqrt(t2 / d2), 1.0)
+        f = 1.0 - rho
+        h_c = np.where(rect[..., None], hc - f[..., None] * d, hc)
+        h_n = np.where(rect, rho * hn, hn)
+        np1 = h_n + 1.0
+        n_new = np.where(np1 < float(p["max_history"]), np1, float(p["max_history"]))
+        a = 1.0 / n_new
+        b = 1.0 - a
+        c_new = h_c + a[..., None] * (c - h_c)
+        v_new = (a * a) * v + (b * b) * hv
+        hist = np.zeros((h, w, HISTORY_DOUBLES))
+        hist[..., H_COL] = np.where(blend[..., None], c_new, c)
+        hist[..., H_VAR] = np.where(blend, v_new, v)
+        hist[..., H_N] = np.where(blend, n_new, np.where(fin, 1.0, 0.0))
+        hist[..., H_RHO] = rho
+        out_rgba = np.ones((h, w, 4))
+        out_rgba[..., :3] = hist[..., H_COL]
+        out_se = np.sqrt(hist[..., H_VAR])
+    res = (hist.reshape(-1), out_rgba.reshape(-1), out_se.reshape(-1))
+    return res + (dict(m=m, d2=d2, T2=t2, rho=rho),) if details else res
+
+
 def orbit_camera(camera_record, degrees):
     """A copy of the camera record whose inverse is rotate_y(degrees) * inverse: the camera orbits about
     the world y axis through the origin (CLCamera carries no from / to to rebuild a view from).  The
@@ -296,7 +416,7 @@ def move_object(objects, index, matrix):
 
 
 def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise=False, reproject_params=None,
-                    denoise_params=None, chunks=0, stream=None, objects=None):
+                    denoise_params=None, chunks=0, stream=None, objects=None, rectify=None):
     """Render one frame per camera record of `cameras` from the resident `scene` (api.Scene), per frame k:
     set_camera, fill_seeds(seed_stream + k), render_moments, error_map, finalize, features, and with
     `temporal` reproject against frame k - 1, with `denoise` the a-trous filter on the result.
@@ -305,6 +425,11 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
     frame.  Frame k then starts with set_objects(objects[k]) before its set_camera, and with `temporal`
     its history is found through motion_table(objects[k - 1], objects[k]) and reproject_motion, which
     follows each object's motion.
+
+    `rectify`: None -- the calls above; True or a dict of ptmi_rectify_params fields (with `temporal`) --
+    history_gather (with the motion table when `objects` is given) and then rectify take the place of the
+    reprojection call: the history is tested against the frame before the blend, and frames also carry
+    rho (W*H, 1.0 where the history was left as found).  max_history is then rectify's.
 
     A generator: yields per frame a dict of float64 torch tensors on the scene's device -- image, se (the
     frame as rendered), feat, out, out_se (what the frame shows: accumulated and / or filtered; image and
@@ -317,6 +442,10 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
 
     if samples <= 0:
         raise ValueError("samples must be positive")
+    if rectify is not None and rectify is not False and not temporal:
+        raise ValueError("rectify needs temporal")
+    rect = None if rectify is None or rectify is False or not temporal else \
+        api.RectifyParams(**{k: v for k, v in rectify_params_dict(rectify).items()})
     w, h = scene.width, scene.height
     npix = w * h
     st = torch.cuda.current_stream() if stream is None else stream
@@ -331,6 +460,10 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
                      dn=torch.empty(npix * 4, **kw), dn_se=torch.empty(npix, **kw)) for _ in range(2)]
         work = torch.empty(api.denoise_work_bytes(w, h) // 8, **kw) if denoise else None
         motion = torch.empty(api.MOTION_DOUBLES * 16, **kw) if objects is not None and temporal else None
+        gathered = torch.empty(npix * HISTORY_DOUBLES, **kw) if rect is not None else None
+        if rect is not None:
+            for buf in ring:
+                buf["rho"] = torch.empty(npix, **kw)
     prev, prev_cam, prev_objs, n_obj = None, None, None, 0
     frame_objects = iter(objects) if objects is not None else None
     for k, cam in enumerate(cameras):
@@ -350,7 +483,18 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
             scene.finalize(sums.data_ptr(), cur["image"].data_ptr(), samples, stream=sp)
             scene.features(cur["feat"].data_ptr(), stream=sp)
             frame = dict(image=cur["image"], se=cur["se"], feat=cur["feat"], out=cur["image"], out_se=cur["se"])
-            if temporal and motion is not None and prev is not None:
+            if rect is not None:
+                moving = motion is not None and prev is not None
+                api.history_gather(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
+                                   prev["hist"].data_ptr() if prev else 0, prev["feat"].data_ptr() if prev else 0,
+                                   prev_cam, w, h, gathered.data_ptr(), motion_ptr=motion.data_ptr() if moving else 0,
+                                   n_obj=n_obj if moving else 0, params=reproject_params, stream=sp)
+                api.rectify(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(), gathered.data_ptr(),
+                            w, h, cur["hist"].data_ptr(), out_rgba_ptr=cur["accumulated"].data_ptr(),
+                            out_se_ptr=cur["accumulated_se"].data_ptr(), params=rect, stream=sp)
+                cur["rho"].copy_(cur["hist"].view(npix, HISTORY_DOUBLES)[:, H_RHO])
+                frame.update(rho=cur["rho"])
+            elif temporal and motion is not None and prev is not None:
                 api.reproject_motion(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
                                      prev["hist"].data_ptr(), prev["feat"].data_ptr(), prev_cam, w, h,
                                      cur["hist"].data_ptr(), motion.data_ptr(), n_obj,
