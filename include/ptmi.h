@@ -282,6 +282,36 @@ int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width,
 int ptmi_scene_features(ptmi_scene* s, double* feat_dev, void* hip_stream, char* err, size_t err_len);
 
 /*
+ * Specular-chain feature buffers: the same records, for the first surface behind mirrors and glass.
+ * The pinhole ray is followed deterministically from its first hit to the first surface that is not
+ * specular, and that surface is recorded at its virtual position, unfolded along the camera ray, so
+ * the image in a planar mirror has the records of the mirrored scene.  Per pixel, with inside = false,
+ * L = 0, tint m = (1, 1, 1), U = I (3x3) and k = 0, at each hit (t, pos, eye-facing unit normal n and
+ * colour c as above, textures included) L += t, then the first rule that applies:
+ *   1. final, if the object is emissive (emission[0] > 0) or k == max_chain;
+ *   2. reflect, if reflectivity >= reflect_min: rd = rd - 2 (rd . n) n from pos,
+ *      m *= c (the bounce record of a reflection tints the path), U = U (I - 2 n n^T), k++;
+ *   3. thin glass (refractive index -1): straight on from pos, k++;
+ *   4. glass (refractive index != 1): with s2 = nr^2 (1 - (n . eye)^2), nr = ri when inside and 1 / ri
+ *      otherwise, total internal reflection (s2 > 1) takes rule 2's step; otherwise the refracted
+ *      direction from pos, inside flips, k++ (no tint);
+ *   5. final otherwise.
+ * A segment starts at pos itself (the trace kernels start EPSILON off the surface along n): no hit is
+ * taken at t <= EPSILON, so the surface just left is not met again, and the unfolded ray is the true one.
+ * The final record: [0..2] = origin + rd0 * L, [3] = L, [4..6] = U n negated where it does not
+ * face -rd0, [7] the final object's index, [8..10] = m * c, [11] = k as a double.  A miss on any
+ * segment, or a direction that is not finite, writes id -1, zeros in [0..10] and k in [11].  A pixel
+ * with k == 0 has ptmi_scene_features' record bit for bit.  The virtual position is exact for chains
+ * of planar mirrors and approximate for curved mirrors and refraction; a pixel follows one branch
+ * (glass is guided by what is behind it, not by its Fresnel reflection).
+ * PTMI_ERR_ARG (and no launch) for a NULL scene or buffer, a buffer that is not 16-byte aligned,
+ * max_chain outside [1, 16], or reflect_min NaN or outside (0, 1].  Allocates nothing; asynchronous
+ * on the stream.
+ */
+int ptmi_scene_features_chain(ptmi_scene* s, double* feat_dev, uint32_t max_chain, double reflect_min,
+                              void* hip_stream, char* err, size_t err_len);
+
+/*
  * A variance-guided, edge-avoiding a-trous wavelet filter (the spatial part of SVGF) over a frame:
  *   rgba_dev  the frame (ptmi_finalize / ptmi_finalize_counts), W*H*4
  *   se_dev    its standard-error map (ptmi_error_map), W*H: the filter's variance is se^2

@@ -1258,6 +1258,22 @@ int ptmi_scene_features(ptmi_scene* s, double* feat_dev, void* hip_stream, char*
     return PTMI_OK;
 }
 
+int ptmi_scene_features_chain(ptmi_scene* s, double* feat_dev, uint32_t max_chain, double reflect_min,
+                              void* hip_stream, char* err, size_t err_len) {
+    if (!s || !feat_dev || ((uintptr_t)feat_dev & 15u)) {
+        set_err(err, err_len, "bad feature-pass arguments");
+        return PTMI_ERR_ARG;
+    }
+    if (max_chain < 1 || max_chain > 16 || !(reflect_min > 0.0 && reflect_min <= 1.0)) {  // (a NaN fails both)
+        set_err(err, err_len, "bad specular-chain parameters (max_chain %u, 1..16; reflect_min %g, (0, 1])", max_chain,
+                reflect_min);
+        return PTMI_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_features_chain(s->dev, feat_dev, max_chain, reflect_min, (hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
 size_t ptmi_denoise_work_bytes(uint32_t width, uint32_t height) {
     return (size_t)width * (size_t)height * 2 * 4 * sizeof(double);  // two (r, g, b, var) states
 }

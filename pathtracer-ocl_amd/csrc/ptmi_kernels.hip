@@ -3131,31 +3131,18 @@ hipError_t launch_camera_terms(const DevScene& S, hipStream_t st) {
 // with its gate chain -- in the one generic instantiation (double4 arithmetic, 32-bit LDS stack,
 // texture lookups), which gives the affine forms' bits.  The normal and the colour restate the head
 // of bounce_shade and its bounce record (tracer.cl:903-955, 1071-1092) rather than share helpers with
-// it: one ray per pixel, and the trace kernels keep their ISA.
+// it: one ray per pixel, and the trace kernels keep their ISA.  They are feature_surface, shared with
+// the specular-chain kernel below.
 static constexpr int kFeatFL = F_ALL | F_PROJ | F_TEX;
-__global__ __launch_bounds__(kBlock) void scene_features(DevScene S, double* __restrict__ feat) {
-    constexpr bool A = false;
-    __shared__ int stk_lds[kStack * kStkStride];
-    const int t = threadIdx.x, W = S.cam.width, H = S.cam.height, tiles_x = (W + kTile - 1) / kTile;
-    const int px = (int)(blockIdx.x % (uint32_t)tiles_x) * kTile + (t & 7);
-    const int py = (int)(blockIdx.x / (uint32_t)tiles_x) * kTile + (t >> 3);
-    if (px >= W || py >= H) return;
-    d4 ro, rd;
-    ray_for_pixel<false, A>(S.cam, nullptr, (unsigned)px, (unsigned)py, 0.5f, 0.5f, 0, ro, rd);
-    Hit h = find_closest_prims<kFeatFL>(S, ro, rd);
-    if (S.run_end[4] > S.run_end[3]) group_walks<A>(S, lds_ptr(stk_lds + t), ro, rd, h);
-    double2* o = reinterpret_cast<double2*>(feat + 12 * ((size_t)py * W + px));
-    if (h.pk < 0) {
-        o[0] = o[1] = o[2] = o[4] = o[5] = make_double2(0.0, 0.0);
-        o[3] = make_double2(0.0, -1.0);
-        return;
-    }
-    const DevObject& ob = S.objs[h.pk & 0xFFFF];
+
+// A hit's eye-facing world normal and the colour of its bounce record, for the ray direction rd that
+// reached pos: what both feature kernels record of a surface.
+template <bool A>
+__device__ __forceinline__ void feature_surface(const DevScene& S, const DevObject& ob, const Hit& h, d4 pos, d4 rd,
+                                                d4& nv, double& cr, double& cg, double& cb) {
     const int type = ob.type;
-    const d4 pos = add4(ro, scl4(rd, h.t));
     const d4 eye = mk(-rd.x, -rd.y, -rd.z, -rd.w);
     // Object normal -> world normal (bounce_shade; tracer.cl:903-955).
-    d4 nv;
     if (type == 0 && !ob.tex_nm) {
         nv = ld4(ob.plane_n);
     } else {
@@ -3194,7 +3181,6 @@ __global__ __launch_bounds__(kBlock) void scene_features(DevScene S, double* __r
     }
     if (dotv<A>(eye, nv) < 0.0) nv = scl4(nv, -1.0);
     // The colour of the bounce record (tracer.cl:1071-1092): an emissive hit keeps its colour too.
-    double cr, cg, cb;
     if (type == 4) {
         const DevTriShade& T = S.tri_shade[h.tri];
         cr = T.color[0], cg = T.color[1], cb = T.color[2];
@@ -3202,6 +3188,30 @@ __global__ __launch_bounds__(kBlock) void scene_features(DevScene S, double* __r
         cr = ob.color[0], cg = ob.color[1], cb = ob.color[2];
         if (ob.tex) textured_color<A>(S.tex[type == 0 ? 0 : type == 1 ? 1 : 2], ob, pos, cr, cg, cb);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void scene_features(DevScene S, double* __restrict__ feat) {
+    constexpr bool A = false;
+    __shared__ int stk_lds[kStack * kStkStride];
+    const int t = threadIdx.x, W = S.cam.width, H = S.cam.height, tiles_x = (W + kTile - 1) / kTile;
+    const int px = (int)(blockIdx.x % (uint32_t)tiles_x) * kTile + (t & 7);
+    const int py = (int)(blockIdx.x / (uint32_t)tiles_x) * kTile + (t >> 3);
+    if (px >= W || py >= H) return;
+    d4 ro, rd;
+    ray_for_pixel<false, A>(S.cam, nullptr, (unsigned)px, (unsigned)py, 0.5f, 0.5f, 0, ro, rd);
+    Hit h = find_closest_prims<kFeatFL>(S, ro, rd);
+    if (S.run_end[4] > S.run_end[3]) group_walks<A>(S, lds_ptr(stk_lds + t), ro, rd, h);
+    double2* o = reinterpret_cast<double2*>(feat + 12 * ((size_t)py * W + px));
+    if (h.pk < 0) {
+        o[0] = o[1] = o[2] = o[4] = o[5] = make_double2(0.0, 0.0);
+        o[3] = make_double2(0.0, -1.0);
+        return;
+    }
+    const DevObject& ob = S.objs[h.pk & 0xFFFF];
+    const d4 pos = add4(ro, scl4(rd, h.t));
+    d4 nv;
+    double cr, cg, cb;
+    feature_surface<A>(S, ob, h, pos, rd, nv, cr, cg, cb);
     o[0] = make_double2(pos.x, pos.y);
     o[1] = make_double2(pos.z, h.t);
     o[2] = make_double2(nv.x, nv.y);
@@ -3210,10 +3220,130 @@ __global__ __launch_bounds__(kBlock) void scene_features(DevScene S, double* __r
     o[5] = make_double2(cb, 0.0);
 }
 
+// ---- Specular-chain features (ptmi_scene_features_chain) ------------------------------------
+// The same ray followed through mirrors and glass to the first surface that is neither, for the
+// filters' guides (include/ptmi.h states the rules).  Each segment is scene_features'
+// hit.  The path is unfolded along the camera ray: the record's position is origin + rd0 * L with L
+// the segments' summed t, and its normal is carried back through the mirrors by U, the product of
+// their Householder matrices I - 2 n n^T -- nine doubles per lane, in registers (one wave per block,
+// no spill).  A segment starts at the hit point itself, not bounce_shade's EPSILON off the surface along
+// the normal: the intersectors take no hit at t <= EPSILON, which keeps the surface just left out, and a
+// start beside the surface would run the unfolded ray beside the true one -- the image in a planar
+// mirror would then not be the mirrored scene's record.  A pixel whose first hit is final (k == 0) stores scene_features' expressions, so its
+// record has that kernel's bits.
+__global__ __launch_bounds__(kBlock) void scene_features_chain(DevScene S, double* __restrict__ feat,
+                                                               uint32_t max_chain, double reflect_min) {
+    constexpr bool A = false;
+    __shared__ int stk_lds[kStack * kStkStride];
+    const int t = threadIdx.x, W = S.cam.width, H = S.cam.height, tiles_x = (W + kTile - 1) / kTile;
+    const int px = (int)(blockIdx.x % (uint32_t)tiles_x) * kTile + (t & 7);
+    const int py = (int)(blockIdx.x / (uint32_t)tiles_x) * kTile + (t >> 3);
+    if (px >= W || py >= H) return;
+    d4 ro, rd;
+    ray_for_pixel<false, A>(S.cam, nullptr, (unsigned)px, (unsigned)py, 0.5f, 0.5f, 0, ro, rd);
+    const d4 ro0 = ro, rd0 = rd;
+    double2* o = reinterpret_cast<double2*>(feat + 12 * ((size_t)py * W + px));
+    double L = 0.0, mr = 1.0, mg = 1.0, mb = 1.0;
+    double u00 = 1.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 1.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 1.0;
+    uint32_t k = 0;
+    bool inside = false;
+    for (;;) {
+        Hit h;
+        h.pk = -1;
+        if (k == 0 || ((fabs(rd.x) + fabs(rd.y)) + fabs(rd.z)) < __builtin_huge_val()) {  // (false for a NaN too)
+            h = find_closest_prims<kFeatFL>(S, ro, rd);
+            if (S.run_end[4] > S.run_end[3]) group_walks<A>(S, lds_ptr(stk_lds + t), ro, rd, h);
+        }
+        if (h.pk < 0) {
+            o[0] = o[1] = o[2] = o[4] = make_double2(0.0, 0.0);
+            o[3] = make_double2(0.0, -1.0);
+            o[5] = make_double2(0.0, (double)k);
+            return;
+        }
+        const DevObject& ob = S.objs[h.pk & 0xFFFF];
+        const d4 pos = add4(ro, scl4(rd, h.t));
+        d4 nv;
+        double cr, cg, cb;
+        feature_surface<A>(S, ob, h, pos, rd, nv, cr, cg, cb);
+        L = L + h.t;
+        // The deterministic branch of bounce_shade's material decision: its random draws become
+        // thresholds (reflect_min) or the transmitted branch (glass).
+        bool reflecting = false, through = false;
+        if (!(ob.emission[0] > 0.0) && k < max_chain) {
+            const double ri = ob.refractive_index;
+            if (ob.reflectivity >= reflect_min) {
+                reflecting = true;
+            } else if (ri == -1.0) {
+                through = true;
+            } else if (ri != 1.0) {
+                const d4 eye = mk(-rd.x, -rd.y, -rd.z, -rd.w);
+                const double nr = inside ? ri / 1.0 : 1.0 / ri;
+                const double ci = dotv<A>(eye, nv);
+                const double s2 = (nr * nr) * (1.0 - (ci * ci));  // refracted's
+                if (s2 > 1.0) {
+                    reflecting = true;
+                } else {
+                    rd = inside ? refracted<A>(eye, nv, ri, 1.0) : refracted<A>(eye, nv, 1.0, ri);
+                    inside = !inside;
+                    through = true;
+                }
+            }
+        }
+        if (reflecting) {
+            rd = reflect<A>(rd, nv);
+            ro = pos;
+            mr = mr * cr, mg = mg * cg, mb = mb * cb;
+            // U = U (I - 2 n n^T) = U - (2 U n) n^T
+            const double a0 = 2.0 * ((u00 * nv.x + u01 * nv.y) + u02 * nv.z);
+            const double a1 = 2.0 * ((u10 * nv.x + u11 * nv.y) + u12 * nv.z);
+            const double a2 = 2.0 * ((u20 * nv.x + u21 * nv.y) + u22 * nv.z);
+            u00 = u00 - a0 * nv.x, u01 = u01 - a0 * nv.y, u02 = u02 - a0 * nv.z;
+            u10 = u10 - a1 * nv.x, u11 = u11 - a1 * nv.y, u12 = u12 - a1 * nv.z;
+            u20 = u20 - a2 * nv.x, u21 = u21 - a2 * nv.y, u22 = u22 - a2 * nv.z;
+            k++;
+            continue;
+        }
+        if (through) {
+            ro = pos;
+            k++;
+            continue;
+        }
+        if (k == 0) {  // scene_features' record, bit for bit (U n and 1.0 * c would lose a -0.0)
+            o[0] = make_double2(pos.x, pos.y);
+            o[1] = make_double2(pos.z, h.t);
+            o[2] = make_double2(nv.x, nv.y);
+            o[3] = make_double2(nv.z, (double)ob.key);
+            o[4] = make_double2(cr, cg);
+            o[5] = make_double2(cb, 0.0);
+            return;
+        }
+        const d4 vp = add4(ro0, scl4(rd0, L));
+        double nx = (u00 * nv.x + u01 * nv.y) + u02 * nv.z;
+        double ny = (u10 * nv.x + u11 * nv.y) + u12 * nv.z;
+        double nz = (u20 * nv.x + u21 * nv.y) + u22 * nv.z;
+        if (((rd0.x * nx + rd0.y * ny) + rd0.z * nz) > 0.0) nx = -nx, ny = -ny, nz = -nz;
+        o[0] = make_double2(vp.x, vp.y);
+        o[1] = make_double2(vp.z, L);
+        o[2] = make_double2(nx, ny);
+        o[3] = make_double2(nz, (double)ob.key);
+        o[4] = make_double2(mr * cr, mg * cg);
+        o[5] = make_double2(mb * cb, (double)k);
+        return;
+    }
+}
+
 hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st) {
     const uint32_t tiles = (uint32_t)((S.cam.width + kTile - 1) / kTile) * (uint32_t)((S.cam.height + kTile - 1) / kTile);
     if (tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(scene_features, dim3(tiles), dim3(kBlock), 0, st, S, feat);
+    return hipGetLastError();
+}
+
+hipError_t launch_features_chain(const DevScene& S, double* feat, uint32_t max_chain, double reflect_min,
+                                 hipStream_t st) {
+    const uint32_t tiles = (uint32_t)((S.cam.width + kTile - 1) / kTile) * (uint32_t)((S.cam.height + kTile - 1) / kTile);
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(scene_features_chain, dim3(tiles), dim3(kBlock), 0, st, S, feat, max_chain, reflect_min);
     return hipGetLastError();
 }
 

@@ -19,6 +19,8 @@ hipError_t launch_plane_normals(DevObject* objs, int n, hipStream_t st);
 hipError_t launch_camera_terms(const DevScene& S, hipStream_t st);
 hipError_t launch_hemi_table(double* out, int* mismatch, hipStream_t st);
 hipError_t launch_features(const DevScene& S, double* feat, hipStream_t st);
+hipError_t launch_features_chain(const DevScene& S, double* feat, uint32_t max_chain, double reflect_min,
+                                 hipStream_t st);
 const void* trace_kernel_symbol(int flags);
 int trace_kernel_flags(int flags);
 int trace_block_threads(int flags);

@@ -27,6 +27,9 @@
 // Alone it renders every sample with moments, in batches of --batch; with --noise-target or --adaptive
 // it filters the frame those loops stop at, and --error-map then holds the filtered standard error.
 // --features FILE writes the first-hit normals as a .raw image (RGB = n * 0.5 + 0.5).
+// --guides first|specular (default first) picks the guide records of --denoise, --temporal, --rectify and
+// --features: the first hits, or the first surface behind mirrors and glass at its virtual position
+// (ptmi_scene_features_chain; --max-chain N, 1..16, default 8, bounds the chain).  Not with --move-object.
 // --frames N (N > 1, one GPU) renders N views from one resident scene (ptmi_scene_set_camera): frame k's
 // camera is the scene's turned by k x --orbit-step degrees about the world y axis (ptmi/temporal.py
 // orbit_camera: inverse' = rotate_y * inverse, Go's Sin and Cos), its seeds come from --seed + k, and its
@@ -83,7 +86,16 @@ struct Cfg {
     bool rectify = false, have_gamma = false, have_radius = false, have_emission = false;
     double rectify_gamma = 3.0, emission_step = 1.0;
     int rectify_radius = 3;
+    std::string guides = "first";
+    int max_chain = 8;
+    bool have_guides = false, have_chain = false;
 };
+
+// The guide records of the scene's camera: the first hits, or with --guides specular the chains' final surfaces.
+int trace_guides(const Cfg& c, ptmi_scene* sc, double* feat, char* err, size_t err_len) {
+    if (c.guides == "specular") return ptmi_scene_features_chain(sc, feat, (uint32_t)c.max_chain, 0.5, nullptr, err, err_len);
+    return ptmi_scene_features(sc, feat, nullptr, err, err_len);
+}
 
 [[noreturn]] void usage(const char* msg) {
     std::fprintf(stderr,
@@ -94,7 +106,7 @@ struct Cfg {
                  "          [--adaptive] [--sample-map FILE.raw] [--denoise] [--denoise-iters N]\n"
                  "          [--features FILE.raw] [--frames N] [--orbit-step DEGREES] [--temporal] [--max-history N]\n"
                  "          [--move-object I --move-step DX,DY,DZ] [--rectify] [--rectify-gamma G] [--rectify-radius R]\n"
-                 "          [--emission-step F]\n",
+                 "          [--emission-step F] [--guides first|specular] [--max-chain N]\n",
                  msg);
     std::exit(2);
 }
@@ -152,6 +164,8 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--rectify-gamma") c.rectify_gamma = std::atof(val().c_str()), c.have_gamma = true;
         else if (a == "--rectify-radius") c.rectify_radius = std::atoi(val().c_str()), c.have_radius = true;
         else if (a == "--emission-step") c.emission_step = std::atof(val().c_str()), c.have_emission = true;
+        else if (a == "--guides") c.guides = val(), c.have_guides = true;
+        else if (a == "--max-chain") c.max_chain = std::atoi(val().c_str()), c.have_chain = true;
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
@@ -187,6 +201,12 @@ Cfg parse(int argc, char** argv) {
     if (c.have_emission && !sequence) usage("--emission-step needs --frames N with N > 1");
     if (c.have_emission && !(std::isfinite(c.emission_step) && c.emission_step >= 0.0)) usage("--emission-step must be finite and >= 0");
     if (c.temporal && c.samples < 2) usage("--temporal needs --samples >= 2 (the variance of a frame)");
+    if (c.guides != "first" && c.guides != "specular") usage("--guides first|specular");
+    if (c.have_guides && !(c.denoise || c.temporal || !c.features.empty()))
+        usage("--guides needs --denoise, --temporal or --features");
+    if (c.have_chain && c.guides != "specular") usage("--max-chain needs --guides specular");
+    if (c.have_chain && (c.max_chain < 1 || c.max_chain > 16)) usage("--max-chain must be 1..16");
+    if (c.guides == "specular" && c.have_move) usage("--guides specular does not follow --move-object");
     if (c.batch <= 0 || (c.have_target && !(c.noise_target >= 0.0))) usage("--batch must be positive, --noise-target >= 0");
     return c;
 }
@@ -229,7 +249,7 @@ int render_noise(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex, 
         const double* se_final = se;
         if (c.denoise || !c.features.empty()) {
             if (hip(hipMalloc((void**)&feat, n * PTMI_FEATURE_DOUBLES * sizeof(double)), "hipMalloc")) return false;
-            if ((rc = ptmi_scene_features(sc, feat, nullptr, err, err_len))) return false;
+            if ((rc = trace_guides(c, sc, feat, err, err_len))) return false;
         }
         if (!c.features.empty()) {
             std::vector<double> fh(n * PTMI_FEATURE_DOUBLES);
@@ -437,7 +457,7 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             if ((rc = ptmi_finalize(sums, image, (uint32_t)n, samples, nullptr, err, err_len))) break;
             const double *frame = image, *frame_se = se;
             double* f = feat[k & 1];
-            if (guides && (rc = ptmi_scene_features(sc, f, nullptr, err, err_len))) break;
+            if (guides && (rc = trace_guides(c, sc, f, err, err_len))) break;
             if (c.temporal) {
                 ptmi_reproject_params rp{32, 0, 0.9, 0.02, 0.05};
                 if (c.max_history) rp.max_history = (uint32_t)c.max_history;

@@ -41,7 +41,7 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts", "ptmi_scene_features",
            "ptmi_denoise", "ptmi_denoise_work_bytes", "ptmi_scene_set_camera", "ptmi_reproject",
            "ptmi_scene_set_objects", "ptmi_motion_table", "ptmi_reproject_motion", "ptmi_history_gather",
-           "ptmi_rectify")
+           "ptmi_rectify", "ptmi_scene_features_chain")
 FEATURE_DOUBLES = 12    # PTMI_FEATURE_DOUBLES: doubles per pixel of Scene.features
 HISTORY_DOUBLES = 8     # PTMI_HISTORY_DOUBLES: doubles per pixel of a reproject history
 MOTION_DOUBLES = 24     # PTMI_MOTION_DOUBLES: doubles per object of a motion table
@@ -153,6 +153,9 @@ def load_library(path=None):
         lib.ptmi_denoise_work_bytes.argtypes = [u32, u32]
         lib.ptmi_denoise.restype = i32
         lib.ptmi_denoise.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(DenoiseParams), vp, vp, vp, sz, vp, cp, sz]
+    if hasattr(lib, "ptmi_scene_features_chain"):  # (likewise)
+        lib.ptmi_scene_features_chain.restype = i32
+        lib.ptmi_scene_features_chain.argtypes = [vp, vp, u32, ctypes.c_double, vp, cp, sz]
     if hasattr(lib, "ptmi_reproject"):  # (likewise)
         lib.ptmi_scene_set_camera.restype = i32
         lib.ptmi_scene_set_camera.argtypes = [vp, vp, cp, sz]
@@ -443,10 +446,18 @@ class Scene:
                                      self.width * self.height, samples, ctypes.c_void_p(stream), err, len(err))
         _check(rc, err)
 
-    def features(self, feat_ptr, stream=0):
+    def features(self, feat_ptr, stream=0, chain=False, max_chain=8, reflect_min=0.5):
         """ptmi_scene_features: the first-hit records of the pinhole rays through the pixel centres,
-        W*H*FEATURE_DOUBLES doubles at feat_ptr (position, t, normal, object id, albedo, 0)."""
+        W*H*FEATURE_DOUBLES doubles at feat_ptr (position, t, normal, object id, albedo, 0).
+        chain=True: ptmi_scene_features_chain instead -- the rays followed through at most max_chain
+        mirrors (reflectivity >= reflect_min) and glass interfaces to the first surface that is neither,
+        recorded at its virtual position, with the chain's length in slot [11]."""
         err = ctypes.create_string_buffer(256)
+        if chain:
+            _check(self._lib.ptmi_scene_features_chain(self._h, ctypes.c_void_p(feat_ptr or None), int(max_chain),
+                                                       float(reflect_min), ctypes.c_void_p(stream), err, len(err)),
+                   err)
+            return
         _check(self._lib.ptmi_scene_features(self._h, ctypes.c_void_p(feat_ptr or None), ctypes.c_void_p(stream), err,
                                              len(err)), err)
 

@@ -10,7 +10,9 @@ device's order; ``exp`` is the one operation whose last bits may differ between 
 some other loop produced (``error.render_to_noise`` / ``error.render_adaptive`` with ``denoise=True``).
 
 The guides are the pinhole ray through each pixel's centre: depth-of-field blur and sub-pixel edges are
-not in them, and the first hit on glass or a mirror says little about what the pixel shows.
+not in them.  With ``guides="first"`` (the default) they are the first hit, which on glass or a mirror
+says little about what the pixel shows; ``guides="specular"`` follows the ray through mirrors and glass
+to the first surface that is neither (ptmi_scene_features_chain).
 """
 import numpy as np
 
@@ -23,6 +25,15 @@ H_TAPS = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)  # the B3 spl
 G_TAPS = (1.0 / 4.0, 1.0 / 2.0, 1.0 / 4.0)  # the variance prefilter: 1/4, 1/8, 1/16 as products
 ALBEDO_FLOOR = 1e-3
 EPS = 1e-12
+GUIDES = ("first", "specular")
+
+
+def trace_guides(scene, feat_ptr, guides="first", stream=0):
+    """The guide records of `scene` at feat_ptr: the first hits (ptmi_scene_features) or, with
+    guides="specular", the specular chains' final surfaces (ptmi_scene_features_chain, its defaults)."""
+    if guides not in GUIDES:
+        raise ValueError("guides must be one of %r, got %r" % (GUIDES, guides))
+    scene.features(feat_ptr, stream=stream, chain=guides == "specular")
 
 
 def params_dict(params=None):
@@ -176,13 +187,16 @@ def normal_image(feat, w, h):
     return out.reshape(-1)
 
 
-def denoise_frame(scene, image, se, params=None, stream=None):
+def denoise_frame(scene, image, se, params=None, stream=None, guides="first"):
     """Denoise a frame of `scene` (api.Scene): `image` (RGBA, W*H*4) and `se` (W*H) are float64 torch
     tensors on the scene's device, as render_to_noise and render_adaptive return them.  Traces the
-    feature pass and runs the filter; returns (denoised image, filtered se, features) as such tensors."""
+    feature pass (`guides`: "first" or "specular") and runs the filter; returns (denoised image,
+    filtered se, features) as such tensors."""
     import torch
     from . import api
 
+    if guides not in GUIDES:
+        raise ValueError("guides must be one of %r, got %r" % (GUIDES, guides))
     npix = scene.width * scene.height
     st = torch.cuda.current_stream() if stream is None else stream
     sp = st.cuda_stream
@@ -190,24 +204,26 @@ def denoise_frame(scene, image, se, params=None, stream=None):
         kw = dict(dtype=torch.float64, device="cuda")
         feat = torch.empty(npix * FEATURE_DOUBLES, **kw)
         out, out_se = torch.empty(npix * 4, **kw), torch.empty(npix, **kw)
-        scene.features(feat.data_ptr(), stream=sp)
+        trace_guides(scene, feat.data_ptr(), guides, stream=sp)
         api.denoise(image.data_ptr(), se.data_ptr(), feat.data_ptr(), scene.width, scene.height, out.data_ptr(),
                     out_se_ptr=out_se.data_ptr(), params=params, stream=sp)
     return out, out_se, feat
 
 
-def render_denoised(scene, samples, seeds_ptr, params=None, chunks=0, stream=None):
+def render_denoised(scene, samples, seeds_ptr, params=None, chunks=0, stream=None, guides="first"):
     """Render a `samples`-spp frame of `scene` (api.Scene) with moments and denoise it:
     render_moments -> error_map -> finalize -> features -> denoise, all on one stream.
 
     Returns (denoised, denoised_se, image, se, feat): float64 torch tensors on the scene's device --
     the filtered RGBA frame and its standard-error map, the frame and map that went in, and the
-    first-hit records."""
+    guide records (`guides`: "first" or "specular")."""
     import torch
     from . import api
 
     if samples <= 0:
         raise ValueError("samples must be positive")
+    if guides not in GUIDES:
+        raise ValueError("guides must be one of %r, got %r" % (GUIDES, guides))
     npix = scene.width * scene.height
     st = torch.cuda.current_stream() if stream is None else stream
     sp = st.cuda_stream
@@ -219,5 +235,5 @@ def render_denoised(scene, samples, seeds_ptr, params=None, chunks=0, stream=Non
         api.error_map(sums.data_ptr(), sq.data_ptr(), scene.width, scene.height, stats.data_ptr(),
                       se_ptr=se.data_ptr(), stream=sp)
         scene.finalize(sums.data_ptr(), image.data_ptr(), samples, stream=sp)
-        out, out_se, feat = denoise_frame(scene, image, se, params=params, stream=st)
+        out, out_se, feat = denoise_frame(scene, image, se, params=params, stream=st, guides=guides)
     return out, out_se, image, se, feat

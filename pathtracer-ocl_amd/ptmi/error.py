@@ -115,7 +115,7 @@ def finalize_counts_reference(sums):
 
 
 def render_to_noise(scene, max_samples, batch, target, seeds_ptr, chunks=0, stream=None, denoise=False,
-                    denoise_params=None):
+                    denoise_params=None, guides="first"):
     """Render `scene` (api.Scene) until the frame's relative noise is at most `target`.
 
     Batches [k*batch, (k+1)*batch) of a `max_samples`-spp frame (the last one short if needed) are
@@ -126,7 +126,8 @@ def render_to_noise(scene, max_samples, batch, target, seeds_ptr, chunks=0, stre
 
     Returns (image, se, samples_done, history): float64 torch tensors on the scene's device, RGBA
     of W*H*4 and the standard-error map of W*H, and the per-batch stats[0] / stats[2].  With `denoise`
-    the image and the map are the filtered ones (ptmi/denoise.py denoise_frame, `denoise_params`).
+    the image and the map are the filtered ones (ptmi/denoise.py denoise_frame, `denoise_params`, and
+    `guides`: "first" or "specular").
     """
     import torch
     from . import api
@@ -158,12 +159,12 @@ def render_to_noise(scene, max_samples, batch, target, seeds_ptr, chunks=0, stre
         scene.finalize(sums.data_ptr(), out.data_ptr(), done, stream=sp)
         if denoise:
             from .denoise import denoise_frame
-            out, se, _ = denoise_frame(scene, out, se, params=denoise_params, stream=st)
+            out, se, _ = denoise_frame(scene, out, se, params=denoise_params, stream=st, guides=guides)
     return out, se, done, history
 
 
 def render_adaptive(scene, max_samples, batch, target, seeds_ptr, chunks=0, stream=None, keep_lists=False,
-                    denoise=False, denoise_params=None):
+                    denoise=False, denoise_params=None, guides="first"):
     """Render `scene` (api.Scene) with each 8x8 tile stopping on its own noise.
 
     Round r traces samples [r*batch, (r+1)*batch) of a `max_samples`-spp frame (the last round short
@@ -184,8 +185,8 @@ def render_adaptive(scene, max_samples, batch, target, seeds_ptr, chunks=0, stre
     tensors on the scene's device -- RGBA of W*H*4, the standard-error map and the per-pixel sample
     counts of W*H -- and one (active tiles, threshold, stats[0] / stats[2]) per round.  With
     keep_lists a fifth element: each round's active list, numpy uint32 arrays.  With `denoise` the image
-    and the map are the filtered ones (ptmi/denoise.py denoise_frame, `denoise_params`); the stopping
-    rule does not see the filter.
+    and the map are the filtered ones (ptmi/denoise.py denoise_frame, `denoise_params`, and `guides`:
+    "first" or "specular"); the stopping rule does not see the filter.
     """
     import torch
     from . import api
@@ -230,5 +231,5 @@ def render_adaptive(scene, max_samples, batch, target, seeds_ptr, chunks=0, stre
         scene.finalize_counts(sums.data_ptr(), out.data_ptr(), stream=sp)
         if denoise:
             from .denoise import denoise_frame
-            out, se, _ = denoise_frame(scene, out, se, params=denoise_params, stream=st)
+            out, se, _ = denoise_frame(scene, out, se, params=denoise_params, stream=st, guides=guides)
     return (out, se, counts, history, lists) if keep_lists else (out, se, counts, history)

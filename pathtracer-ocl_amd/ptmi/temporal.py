@@ -416,7 +416,7 @@ def move_object(objects, index, matrix):
 
 
 def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise=False, reproject_params=None,
-                    denoise_params=None, chunks=0, stream=None, objects=None, rectify=None):
+                    denoise_params=None, chunks=0, stream=None, objects=None, rectify=None, guides="first"):
     """Render one frame per camera record of `cameras` from the resident `scene` (api.Scene), per frame k:
     set_camera, fill_seeds(seed_stream + k), render_moments, error_map, finalize, features, and with
     `temporal` reproject against frame k - 1, with `denoise` the a-trous filter on the result.
@@ -431,12 +431,23 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
     reprojection call: the history is tested against the frame before the blend, and frames also carry
     rho (W*H, 1.0 where the history was left as found).  max_history is then rectify's.
 
+    `guides`: "first" -- the first-hit records; "specular" -- the specular chains' final surfaces at their
+    virtual positions (ptmi_scene_features_chain), which the reprojection, the rectification and the filter
+    then use as they use the first hits.  Not together with `objects` (ValueError): a motion record moves
+    real points, and a virtual point behind a mirror moves as the mirrored object does.
+
     A generator: yields per frame a dict of float64 torch tensors on the scene's device -- image, se (the
     frame as rendered), feat, out, out_se (what the frame shows: accumulated and / or filtered; image and
     se themselves without either), and with `temporal` hist (W*H*HISTORY_DOUBLES) and accumulated /
     accumulated_se (the accumulated frame before the filter).  The history and feature ping-pong buffers
     are kept here; a yielded frame's tensors stay valid until the frame after the next is produced, so
     copy what must live longer."""
+    from .denoise import GUIDES, trace_guides
+    if guides not in GUIDES:
+        raise ValueError("guides must be one of %r, got %r" % (GUIDES, guides))
+    if guides == "specular" and objects is not None:
+        raise ValueError("guides=\"specular\" does not follow moving objects (objects=): the motion table moves "
+                         "real points, not the virtual ones behind a mirror")
     import torch
     from . import api
 
@@ -481,7 +492,7 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
                                  stream=sp)
             api.error_map(sums.data_ptr(), sq.data_ptr(), w, h, stats.data_ptr(), se_ptr=cur["se"].data_ptr(), stream=sp)
             scene.finalize(sums.data_ptr(), cur["image"].data_ptr(), samples, stream=sp)
-            scene.features(cur["feat"].data_ptr(), stream=sp)
+            trace_guides(scene, cur["feat"].data_ptr(), guides, stream=sp)
             frame = dict(image=cur["image"], se=cur["se"], feat=cur["feat"], out=cur["image"], out_se=cur["se"])
             if rect is not None:
                 moving = motion is not None and prev is not None
