@@ -377,7 +377,8 @@ int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* fea
  * reprojects the glass, not what shows through it, and the history is trusted wherever the geometry
  * matches: view-dependent shading and changed lighting are the business of ptmi_history_gather +
  * ptmi_rectify, which test the history against the frame; the objects are taken to stand still, only the
- * camera moves (ptmi_reproject_motion follows objects that moved); at 1 spp se is +inf and every pixel resets.
+ * camera moves (ptmi_reproject_motion follows objects that moved); at 1 spp the rendered se is +inf
+ * and every pixel resets: pass ptmi_variance_estimate's map instead.
  * Allocates nothing; asynchronous on the stream.  No output may overlap an input or another output, in
  * whole or in part (callers ping-pong two history buffers; there is no in-place form: out_rgba_dev is
  * not rgba_dev, out_se_dev is not se_dev); the ranges are checked.  Every buffer but se_dev and
@@ -568,6 +569,79 @@ int ptmi_rectify(const double* rgba_dev, const double* se_dev, const double* fea
                  uint32_t width, uint32_t height, const ptmi_rectify_params* params /* NULL = defaults */,
                  double* out_hist_dev, double* out_rgba_dev /* may be NULL */, double* out_se_dev /* may be NULL */,
                  void* hip_stream, char* err, size_t err_len);
+
+/*
+ * The standard error of a frame's pixels, estimated instead of taken from the frame's own samples: the one
+ * input of ptmi_reproject, ptmi_reproject_motion, ptmi_history_gather + ptmi_rectify and ptmi_denoise that a
+ * frame of few samples cannot give (ptmi_error_map: se = +inf at 1 spp, a sample variance that is itself
+ * noise at 2-8 spp, se = 0 where the few paths all missed the light).  Pass out_se_dev to those calls in
+ * the place of the rendered map; with it a sequence of 1-spp frames accumulates.  Two estimates:
+ * TEMPORAL, the first and second moments of each surface point's frames, accumulated through
+ * ptmi_history_gather's lookup on a moment history of this call's own (callers ping-pong two), and
+ * SPATIAL, where that history is shorter than min_temporal, the variance of a window of same-surface pixels
+ * of this frame.
+ *
+ * Moment record, per pixel of out_mom_dev (W*H*PTMI_MOMENT_DOUBLES): [0..2] mu, the accumulated mean colour;
+ * [3] mu2, the accumulated mean of (r r + g g) + b b;  [4] N;  [5] the estimate's source: 0 none, 1 temporal,
+ * 2 spatial, 3 fallback;  [6] the estimated variance;  [7] 0.
+ * Per pixel p with colour c, s = (c_r c_r + c_g c_g) + c_b c_b and first-hit record (x_p, t_p, n_p, id_p):
+ *   NOT FINITE  c not finite: the record is (c, s, N = 0, 0, 0, 0) and out_se = se_p (+inf when se_dev is
+ *           NULL) -- ptmi_reproject's reset: later frames read nothing from it.
+ *   GATHER  exactly ptmi_history_gather's projection, its four taps in its order and its acceptance tests
+ *           (inside the image, N_q > 0 and a finite record, the same id, the normal and the plane distance;
+ *           with a motion table its states 0 / 1 / 2) on prev_mom_dev and prev_feat_dev.  With W the sum of
+ *           the accepted taps' bilinear weights w:
+ *             h_mu.k = c_k + (sum w (mu_q.k - c_k)) / W;  h_mu2 = s + (sum w (mu2_q - s)) / W;  h_N = (sum w N_q) / W
+ *           -- means weighted by w (not the sum w^2 / W^2 weights of ptmi_reproject's h_var).  The resets are the
+ *           gather's: no history (prev_mom_dev NULL), a miss, a point behind the previous camera,
+ *           W < min_weight or W == 0, motion state 2.
+ *   BLEND   reset: mu' = c, mu2' = s, N' = 1.  Else N' = min(h_N + 1, max_history), a = 1 / N',
+ *           mu'_k = h_mu.k + a (c_k - h_mu.k),  mu2' = h_mu2 + a (s - h_mu2).
+ *   TEMPORAL  N' >= min_temporal:  d = mu2' - ((mu'_r mu'_r + mu'_g mu'_g) + mu'_b mu'_b),
+ *           var = (d < 0 ? 0 : d) (N' / (N' - 1)),  source 1.
+ *   SPATIAL otherwise: taps q = p + (dx, dy), dy outer, dx inner, both in [-radius, radius], raster order,
+ *           centre included; ACCEPTED when inside the image, c_q finite and id_q == id_p (a NaN id matches
+ *           nothing, misses match misses), and, when p is a hit (not id_p < 0),
+ *           (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= window_normal_cos.  Sequential, separately rounded
+ *           sums in tap order, D = c_q - c:   m += 1;  e_k += D_k;  b += (D_r D_r + D_g D_g) + D_b D_b.
+ *           m >= min_count:  E = e / m,  d = b / m - ((E_r E_r + E_g E_g) + E_b E_b),
+ *           var = (d < 0 ? 0 : d) (m / (m - 1)),  source 2.
+ *   FALLBACK  otherwise, source 3:  var = se_p^2 when se_dev is given and se_p is finite, else var = s -- the
+ *           pixel's own magnitude, a 100 % relative error: deliberately pessimistic.
+ *   out_mom_dev = (mu', mu2', N', source, var, 0);  out_se_dev = sqrt(var): the standard error of THIS frame's
+ *   pixel value, which is what every consumer of se expects.
+ * A constant sequence comes back with var = 0 and mu' = c bit for bit (the forms written around c and s).  Every
+ * operation is an IEEE add, multiply, divide, square root or comparison; the exact order is ptmi/temporal.py
+ * variance_reference.
+ * Limits: the temporal estimate includes real changes of a surface point's radiance (view-dependent shading,
+ * moving lights) and the spatial one shading gradients and texture inside the window: both then overestimate,
+ * which causes more filtering, not false confidence.  The moment history is not rectified.
+ * Allocates nothing; asynchronous on the stream.  No output may overlap an input or another output; the ranges
+ * are checked.  Every buffer but se_dev and out_se_dev must be 16-byte aligned.
+ * PTMI_ERR_ARG (no launch, no device call) for a NULL required pointer (se_dev, prev_mom_dev and motion_dev may
+ * be NULL; a history needs prev_feat_dev and prev_camera), zero width or height, a parameter outside its range
+ * below, non-zero flags, a negative or non-finite threshold, overlapping or misaligned buffers, a prev_camera
+ * that is singular, not finite or of another width or height, a motion table without objects or objects
+ * without a table, and n_obj above 16.
+ */
+#define PTMI_MOMENT_DOUBLES 8
+typedef struct ptmi_variance_params {
+    uint32_t max_history;   /* default 32; 1..65536 */
+    uint32_t min_temporal;  /* default 4: N' below it -> spatial estimate; 2..65536 */
+    uint32_t radius;        /* spatial window half-size, default 3 (7x7); 1..4 */
+    uint32_t min_count;     /* default 9: fewer accepted window taps -> fallback; >= 2 */
+    uint32_t flags;         /* 0 */
+    double normal_cos, plane_dist, min_weight;  /* the gather's, defaults as ptmi_reproject_params */
+    double window_normal_cos;                   /* default 0.9: window taps on hit pixels need n_p.n_q >= it */
+} ptmi_variance_params;
+
+int ptmi_variance_estimate(const double* rgba_dev, const double* se_dev /* may be NULL */, const double* feat_dev,
+                           const double* prev_mom_dev /* NULL: first frame */, const double* prev_feat_dev,
+                           const void* prev_camera, uint32_t width, uint32_t height,
+                           const ptmi_variance_params* params /* NULL = defaults */,
+                           double* out_mom_dev, double* out_se_dev,
+                           const double* motion_dev /* NULL: static */, uint32_t n_obj,
+                           void* hip_stream, char* err, size_t err_len);
 
 /* Kernel timing: with timing enabled, every trace_kernel launch of the scene is
  * bracketed by HIP events recorded on the launch stream; ptmi_scene_kernel_time

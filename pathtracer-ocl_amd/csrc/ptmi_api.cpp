@@ -1517,6 +1517,28 @@ static bool cofactor_inverse(const double* m, double* out) {
     return true;
 }
 
+// The previous camera's part of a lookup's arguments (ptmi_reproject and its kin, ptmi_variance_estimate):
+// rows 0-2 of its world-to-camera matrix and its pixel mapping.  PTMI_ERR_ARG for a record that is singular,
+// not finite or of another size than the frame.
+static int previous_camera_args(const char* who, const void* prev_camera, uint32_t width, uint32_t height,
+                                ReprojectArgs& a, char* err, size_t err_len) {
+    DevCamera cam{};
+    if (const int rc = convert_camera((const uint8_t*)prev_camera, cam, err, err_len)) return rc;
+    double T[16];
+    if ((uint32_t)cam.width != width || (uint32_t)cam.height != height || !cofactor_inverse(cam.inv, T) ||
+        !(std::isfinite(cam.pixel_size) && cam.pixel_size > 0.0) || !std::isfinite(cam.half_width) ||
+        !std::isfinite(cam.half_height)) {
+        set_err(err, err_len, "%s: bad previous camera (%dx%d for a %ux%u frame, singular or non-finite)", who,
+                cam.width, cam.height, width, height);
+        return PTMI_ERR_ARG;
+    }
+    std::memcpy(a.T, T, sizeof(a.T));  // rows 0-2: the point's camera-space x, y, z
+    a.half_width = cam.half_width;
+    a.half_height = cam.half_height;
+    a.pixel_size = cam.pixel_size;
+    return PTMI_OK;
+}
+
 // ptmi_reproject (motion_dev == NULL, n_obj == 0), ptmi_reproject_motion and ptmi_history_gather (gather:
 // out_hist_dev is the gathered record, and there are no other outputs): one set of checks.
 static int reproject_checked(const double* rgba_dev, const double* se_dev, const double* feat_dev,
@@ -1571,22 +1593,8 @@ static int reproject_checked(const double* rgba_dev, const double* se_dev, const
     a.normal_cos = p.normal_cos;
     a.plane_dist = p.plane_dist;
     a.min_weight = p.min_weight;
-    if (prev_camera) {
-        DevCamera cam{};
-        if (const int rc = convert_camera((const uint8_t*)prev_camera, cam, err, err_len)) return rc;
-        double T[16];
-        if ((uint32_t)cam.width != width || (uint32_t)cam.height != height || !cofactor_inverse(cam.inv, T) ||
-            !(std::isfinite(cam.pixel_size) && cam.pixel_size > 0.0) || !std::isfinite(cam.half_width) ||
-            !std::isfinite(cam.half_height)) {
-            set_err(err, err_len, "reproject: bad previous camera (%dx%d for a %ux%u frame, singular or non-finite)",
-                    cam.width, cam.height, width, height);
-            return PTMI_ERR_ARG;
-        }
-        std::memcpy(a.T, T, sizeof(a.T));  // rows 0-2: the point's camera-space x, y, z
-        a.half_width = cam.half_width;
-        a.half_height = cam.half_height;
-        a.pixel_size = cam.pixel_size;
-    }
+    if (prev_camera)
+        if (const int rc = previous_camera_args("reproject", prev_camera, width, height, a, err, err_len)) return rc;
     if (gather)
         HIP_TRY(launch_history_gather(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev,
                                       motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
@@ -1678,6 +1686,75 @@ int ptmi_rectify(const double* rgba_dev, const double* se_dev, const double* fea
     a.max_history = (double)p.max_history;
     HIP_TRY(launch_rectify(rgba_dev, se_dev, feat_dev, gathered_dev, a, p.radius, out_hist_dev, out_rgba_dev, out_se_dev,
                            (hipStream_t)hip_stream));
+    return PTMI_OK;
+}
+
+int ptmi_variance_estimate(const double* rgba_dev, const double* se_dev, const double* feat_dev,
+                           const double* prev_mom_dev, const double* prev_feat_dev, const void* prev_camera,
+                           uint32_t width, uint32_t height, const ptmi_variance_params* params, double* out_mom_dev,
+                           double* out_se_dev, const double* motion_dev, uint32_t n_obj, void* hip_stream, char* err,
+                           size_t err_len) {
+    ptmi_variance_params p{32, 4, 3, 9, 0, 0.9, 0.02, 0.05, 0.9};
+    if (params) p = *params;
+    if (!rgba_dev || !feat_dev || !out_mom_dev || !out_se_dev || (prev_mom_dev && (!prev_feat_dev || !prev_camera)) ||
+        width == 0 || height == 0 || width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
+        set_err(err, err_len, "bad variance_estimate arguments (%u x %u)", width, height);
+        return PTMI_ERR_ARG;
+    }
+    if ((motion_dev == nullptr) != (n_obj == 0) || n_obj > PTMI_MAX_OBJECTS) {
+        set_err(err, err_len, "bad variance_estimate arguments (motion table %s, %u objects)",
+                motion_dev ? "given" : "NULL", n_obj);
+        return PTMI_ERR_ARG;
+    }
+    auto good = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (p.max_history < 1 || p.max_history > 65536 || p.min_temporal < 2 || p.min_temporal > 65536 || p.radius < 1 ||
+        p.radius > 4 || p.min_count < 2 || p.flags != 0 || !good(p.normal_cos) || !good(p.plane_dist) ||
+        !good(p.min_weight) || !good(p.window_normal_cos)) {
+        set_err(err, err_len,
+                "bad variance parameters (max_history %u min_temporal %u radius %u min_count %u flags %u normal_cos %g "
+                "plane_dist %g min_weight %g window_normal_cos %g)",
+                p.max_history, p.min_temporal, p.radius, p.min_count, p.flags, p.normal_cos, p.plane_dist, p.min_weight,
+                p.window_normal_cos);
+        return PTMI_ERR_ARG;
+    }
+    // No output may overlap an input or another output (the kernel's pointers are __restrict__).
+    const size_t npix = (size_t)width * height;
+    struct Range {
+        const double* p;
+        size_t doubles;
+    };
+    const Range ins[6] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
+                          {prev_mom_dev, npix * PTMI_MOMENT_DOUBLES}, {prev_feat_dev, npix * PTMI_FEATURE_DOUBLES},
+                          {motion_dev, (size_t)n_obj * PTMI_MOTION_DOUBLES}};
+    const Range outs[2] = {{out_mom_dev, npix * PTMI_MOMENT_DOUBLES}, {out_se_dev, npix}};
+    auto overlap = [](const Range& a, const Range& b) {
+        if (!a.p || !b.p) return false;
+        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+        return a0 < b0 + b.doubles * sizeof(double) && b0 < a0 + a.doubles * sizeof(double);
+    };
+    bool aliased = overlap(outs[0], outs[1]);
+    for (int o = 0; o < 2; o++)
+        for (int i = 0; i < 6; i++) aliased = aliased || overlap(outs[o], ins[i]);
+    if (aliased || (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)prev_mom_dev | (uintptr_t)prev_feat_dev |
+                     (uintptr_t)out_mom_dev | (uintptr_t)motion_dev) & 15u)) {
+        set_err(err, err_len, "variance_estimate buffers overlap or are not 16-byte aligned");
+        return PTMI_ERR_ARG;
+    }
+    VarianceArgs a{};
+    a.r.W = (int32_t)width;
+    a.r.H = (int32_t)height;
+    a.r.max_history = (double)p.max_history;
+    a.r.normal_cos = p.normal_cos;
+    a.r.plane_dist = p.plane_dist;
+    a.r.min_weight = p.min_weight;
+    a.min_temporal = (double)p.min_temporal;
+    a.window_normal_cos = p.window_normal_cos;
+    a.min_count = p.min_count;
+    if (prev_camera)
+        if (const int rc = previous_camera_args("variance_estimate", prev_camera, width, height, a.r, err, err_len))
+            return rc;
+    HIP_TRY(launch_variance(rgba_dev, se_dev, feat_dev, prev_mom_dev, prev_feat_dev, a, p.radius, out_mom_dev, out_se_dev,
+                            motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
     return PTMI_OK;
 }
 

@@ -205,6 +205,13 @@ struct ReprojectArgs {
     double half_width, half_height, pixel_size;
     double max_history, normal_cos, plane_dist, min_weight;
 };
+// ptmi_variance_estimate's: the lookup's, and min_temporal (as a double: N' is one), the window's normal
+// threshold and min_count.
+struct VarianceArgs {
+    ReprojectArgs r;
+    double min_temporal, window_normal_cos;
+    uint32_t min_count, pad;
+};
 // ptmi_rectify's: the frame, min_count, gamma * gamma (the host's product, as numpy's) and max_history.
 struct RectifyArgs {
     int32_t W, H;

@@ -1,6 +1,6 @@
 // ptmi_image_kernels.hip -- gfx950 (MI355X / CDNA4) image-space passes: the a-trous denoiser, temporal
-// reprojection, the error map and its summaries, accumulate, finalize, tile selection, the multi-device
-// combine and seed generation, each with its launch wrapper (ptmi_launch.h).
+// reprojection, history rectification, variance estimation, the error map and its summaries, accumulate,
+// finalize, tile selection, the multi-device combine and seed generation, each with its launch wrapper (ptmi_launch.h).
 //
 // They work on frames, records and tile lists alone: nothing here sees a scene, a camera or a PTMI_*
 // build switch, and the only tie to the path tracer (ptmi_kernels.hip) is the tile size kTile.  Compiled
@@ -230,7 +230,78 @@ hipError_t launch_denoise(const double* rgba, const double* se, const double* fe
 }
 
 // ---- Temporal accumulation (ptmi_reproject) ----------------------------------------------------
-// One thread per pixel on the denoise passes' 16 x 16 blocks: a wave covers 4 rows of 16 pixels, so
+// First the lookup reproject_pass and variance_pass share: the pixel's surface point (px, py, pz; t_p = pt) and
+// normal carried back to where they were (kMotion), projected with the previous camera, and the four taps
+// (0,0), (1,0), (0,1), (1,1) tested against the previous frame's 8-double records `prev` (a history or a
+// moment record: [0..3] finite, [4] > 0) and first-hit records.  tap(w, h0, h1, h2) is called per accepted
+// tap, in that order, with its bilinear weight and the first three 16-B pairs of its record; a pixel that
+// resets (no usable motion, a point behind the camera) gets no call.  Forced inline: each caller's sums
+// stay in registers, in the operation order ptmi/temporal.py _history_taps states.
+template <bool kMotion, class Tap>
+__device__ __forceinline__ void history_taps(const ReprojectArgs& a, const double* __restrict__ prev,
+                                             const double* __restrict__ prev_feat, const double* __restrict__ motion,
+                                             int n_obj, double px, double py, double pz, double pt, double n0, double n1,
+                                             double n2, double id, Tap&& tap) {
+    const int W = a.W, H = a.H;
+    // the surface point and its normal as the previous frame saw them
+    double ux = px, uy = py, uz = pz, m0 = n0, m1 = n1, m2 = n2;
+    bool history = true;
+    if (kMotion) {
+        if (id < (double)n_obj) {  // (id >= 0 here; a NaN id fails and stays static)
+            const double2* mr = reinterpret_cast<const double2*>(motion + 24 * (int)id);
+            const double state = mr[10].y;
+            if (state == 1.0) {
+                const double2 b0 = mr[0], b1 = mr[1], b2 = mr[2], b3 = mr[3], b4 = mr[4], b5 = mr[5];
+                const double2 g0 = mr[6], g1 = mr[7], g2 = mr[8], g3 = mr[9], g4 = mr[10];
+                ux = ((b0.x * px + b0.y * py) + b1.x * pz) + b1.y;
+                uy = ((b2.x * px + b2.y * py) + b3.x * pz) + b3.y;
+                uz = ((b4.x * px + b4.y * py) + b5.x * pz) + b5.y;
+                const double e0 = (g0.x * n0 + g0.y * n1) + g1.x * n2;
+                const double e1 = (g1.y * n0 + g2.x * n1) + g2.y * n2;
+                const double e2 = (g3.x * n0 + g3.y * n1) + g4.x * n2;
+                const double l = (e0 * e0 + e1 * e1) + e2 * e2;
+                history = l > 0.0 && isfinite(l);
+                const double len = sqrt(l);
+                m0 = e0 / len;
+                m1 = e1 / len;
+                m2 = e2 / len;
+            } else if (state != 0.0) {
+                history = false;
+            }
+        }
+    }
+    const double* T = a.T;
+    const double qx = ((T[0] * ux + T[1] * uy) + T[2] * uz) + T[3];
+    const double qy = ((T[4] * ux + T[5] * uy) + T[6] * uz) + T[7];
+    const double z = -(((T[8] * ux + T[9] * uy) + T[10] * uz) + T[11]);
+    if (!(history && z > 0.0)) return;
+    const double fu = (a.half_width - qx / z) / a.pixel_size - 0.5;
+    const double fv = (a.half_height - qy / z) / a.pixel_size - 0.5;
+    const double fx0 = floor(fu), fy0 = floor(fv);
+    const double wx = fu - fx0, wy = fv - fy0;
+    const double bound = a.plane_dist * pt;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {  // taps (0,0), (1,0), (0,1), (1,1)
+        const int ti = k & 1, tj = k >> 1;
+        const double tx = fx0 + (double)ti, ty = fy0 + (double)tj;
+        // in double: a NaN or a huge coordinate fails the test before any conversion
+        if (!(tx >= 0.0 && tx < (double)W && ty >= 0.0 && ty < (double)H)) continue;
+        const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
+        const double2* hq = reinterpret_cast<const double2*>(prev + 8 * q);
+        const double2 h0 = hq[0], h1 = hq[1], h2 = hq[2];
+        if (!(h2.x > 0.0) || !dn_finite(h0.x, h0.y, h1.x, h1.y)) continue;
+        const double2* fq = reinterpret_cast<const double2*>(prev_feat + 12 * q);
+        const double2 g0 = fq[0], g1 = fq[1], g2 = fq[2], g3 = fq[3];
+        if (g3.y != id) continue;
+        const double dn = (m0 * g2.x + m1 * g2.y) + m2 * g3.x;
+        if (!(dn >= a.normal_cos)) continue;
+        const double dd = (m0 * (g0.x - ux) + m1 * (g0.y - uy)) + m2 * (g1.x - uz);
+        if (!(fabs(dd) <= bound)) continue;
+        tap((ti ? wx : 1.0 - wx) * (tj ? wy : 1.0 - wy), h0, h1, h2);
+    }
+}
+
+// reproject_pass.  One thread per pixel on the denoise passes' 16 x 16 blocks: a wave covers 4 rows of 16 pixels, so
 // its own loads and stores are 512-B (frame) and 1-KB (history) runs of 16-B accesses, and its taps
 // into the previous frame -- neighbouring pixels project to neighbouring places -- stay within a few
 // rows.  Per pixel 136 B of its own frame, up to four taps of 48 B history and 64 B of a record, 64 B
@@ -243,15 +314,17 @@ hipError_t launch_denoise(const double* rgba, const double* se, const double* fe
 // not wave-uniform -- as 16-B vector loads; a moved object's point and normal are carried back to where
 // they were (x' = B (x_p, 1), n' = G n_p / |G n_p|) before the projection and the tap tests, a static
 // one (or an id outside the table) takes the path below with the current point, bit for bit, and an
-// object without a usable motion resets.  The instantiation without kMotion ignores the two trailing
-// arguments and keeps the instruction stream it had as a plain kernel.
+// object without a usable motion resets (history_taps).  The instantiation without kMotion ignores the two
+// trailing arguments, and its outputs are the plain kernel's bit for bit.
 //
 // kGather (ptmi_history_gather): the same pass up to the blend, which it leaves to ptmi_rectify -- the
 // record is the history as found, (h_c, h_var, h_N), and a pixel that resets writes (c_p, se_p^2, 0): N = 0
 // says that no history was found.  h_c, h_var and h_N are the values the blend below takes, by the same
-// operations in the same order: one kernel text, and what kGather leaves out is left out at compile time, so
-// the instantiations without it keep the instruction stream they had (tools/isa_fingerprint.py).  It
+// operations in the same order: one kernel text, and what kGather leaves out is left out at compile time.  It
 // ignores out_rgba and out_se.
+//
+// Sharing the lookup with variance_pass rescheduled all four instantiations by a few instructions
+// (profiles/variance/SUMMARY.md): they keep their outputs bit for bit, not the instruction stream they had.
 template <bool kMotion, bool kGather>
 __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __restrict__ rgba,
                                                                 const double* __restrict__ se,
@@ -277,85 +350,31 @@ __global__ __launch_bounds__(kDnX * kDnY) void reproject_pass(const double* __re
     // the reset: this frame alone (a pixel that is not finite is no history for the next frame)
     double o0 = c0, o1 = c1, o2 = c2, ov = v, on = kGather ? 0.0 : fin ? 1.0 : 0.0;
     if (prev_hist != nullptr && fin && !(id < 0.0)) {
-        // the surface point and its normal as the previous frame saw them
-        double ux = px, uy = py, uz = pz, m0 = n0, m1 = n1, m2 = n2;
-        bool history = true;
-        if (kMotion) {
-            if (id < (double)n_obj) {  // (id >= 0 here; a NaN id fails and stays static)
-                const double2* mr = reinterpret_cast<const double2*>(motion + 24 * (int)id);
-                const double state = mr[10].y;
-                if (state == 1.0) {
-                    const double2 b0 = mr[0], b1 = mr[1], b2 = mr[2], b3 = mr[3], b4 = mr[4], b5 = mr[5];
-                    const double2 g0 = mr[6], g1 = mr[7], g2 = mr[8], g3 = mr[9], g4 = mr[10];
-                    ux = ((b0.x * px + b0.y * py) + b1.x * pz) + b1.y;
-                    uy = ((b2.x * px + b2.y * py) + b3.x * pz) + b3.y;
-                    uz = ((b4.x * px + b4.y * py) + b5.x * pz) + b5.y;
-                    const double e0 = (g0.x * n0 + g0.y * n1) + g1.x * n2;
-                    const double e1 = (g1.y * n0 + g2.x * n1) + g2.y * n2;
-                    const double e2 = (g3.x * n0 + g3.y * n1) + g4.x * n2;
-                    const double l = (e0 * e0 + e1 * e1) + e2 * e2;
-                    history = l > 0.0 && isfinite(l);
-                    const double len = sqrt(l);
-                    m0 = e0 / len;
-                    m1 = e1 / len;
-                    m2 = e2 / len;
-                } else if (state != 0.0) {
-                    history = false;
-                }
-            }
-        }
-        const double* T = a.T;
-        const double qx = ((T[0] * ux + T[1] * uy) + T[2] * uz) + T[3];
-        const double qy = ((T[4] * ux + T[5] * uy) + T[6] * uz) + T[7];
-        const double z = -(((T[8] * ux + T[9] * uy) + T[10] * uz) + T[11]);
-        if (history && z > 0.0) {
-            const double fu = (a.half_width - qx / z) / a.pixel_size - 0.5;
-            const double fv = (a.half_height - qy / z) / a.pixel_size - 0.5;
-            const double fx0 = floor(fu), fy0 = floor(fv);
-            const double wx = fu - fx0, wy = fv - fy0;
-            const double bound = a.plane_dist * pt;
-            double sw = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0, sv = 0.0, sn = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {  // taps (0,0), (1,0), (0,1), (1,1)
-                const int ti = k & 1, tj = k >> 1;
-                const double tx = fx0 + (double)ti, ty = fy0 + (double)tj;
-                // in double: a NaN or a huge coordinate fails the test before any conversion
-                if (!(tx >= 0.0 && tx < (double)W && ty >= 0.0 && ty < (double)H)) continue;
-                const size_t q = (size_t)(int)ty * W + (size_t)(int)tx;
-                const double2* hq = reinterpret_cast<const double2*>(prev_hist + 8 * q);
-                const double2 h0 = hq[0], h1 = hq[1], h2 = hq[2];
-                if (!(h2.x > 0.0) || !dn_finite(h0.x, h0.y, h1.x, h1.y)) continue;
-                const double2* fq = reinterpret_cast<const double2*>(prev_feat + 12 * q);
-                const double2 g0 = fq[0], g1 = fq[1], g2 = fq[2], g3 = fq[3];
-                if (g3.y != id) continue;
-                const double dn = (m0 * g2.x + m1 * g2.y) + m2 * g3.x;
-                if (!(dn >= a.normal_cos)) continue;
-                const double dd = (m0 * (g0.x - ux) + m1 * (g0.y - uy)) + m2 * (g1.x - uz);
-                if (!(fabs(dd) <= bound)) continue;
-                const double w = (ti ? wx : 1.0 - wx) * (tj ? wy : 1.0 - wy);
-                sw = sw + w;
-                r0 = r0 + w * (h0.x - c0);
-                r1 = r1 + w * (h0.y - c1);
-                r2 = r2 + w * (h1.x - c2);
-                sv = sv + (w * w) * h1.y;
-                sn = sn + w * h2.x;
-            }
-            if (sw >= a.min_weight && sw > 0.0) {
-                // the history's weighted mean written around this frame's colour, and the blend around
-                // the history: a constant sequence stays constant bit for bit
-                const double h0 = c0 + r0 / sw, h1 = c1 + r1 / sw, h2 = c2 + r2 / sw;
-                const double hv = sv / (sw * sw), hn = sn / sw;
-                if constexpr (kGather) {
-                    o0 = h0, o1 = h1, o2 = h2, ov = hv, on = hn;
-                } else {
-                    const double np1 = hn + 1.0;
-                    on = np1 < a.max_history ? np1 : a.max_history;
-                    const double al = 1.0 / on, be = 1.0 - al;
-                    o0 = h0 + al * (c0 - h0);
-                    o1 = h1 + al * (c1 - h1);
-                    o2 = h2 + al * (c2 - h2);
-                    ov = (al * al) * v + (be * be) * hv;
-                }
+        double sw = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0, sv = 0.0, sn = 0.0;
+        history_taps<kMotion>(a, prev_hist, prev_feat, motion, n_obj, px, py, pz, pt, n0, n1, n2, id,
+                              [&](double w, const double2& h0, const double2& h1, const double2& h2) {
+                                  sw = sw + w;
+                                  r0 = r0 + w * (h0.x - c0);
+                                  r1 = r1 + w * (h0.y - c1);
+                                  r2 = r2 + w * (h1.x - c2);
+                                  sv = sv + (w * w) * h1.y;
+                                  sn = sn + w * h2.x;
+                              });
+        if (sw >= a.min_weight && sw > 0.0) {  // (a pixel history_taps reset: W = 0)
+            // the history's weighted mean written around this frame's colour, and the blend around
+            // the history: a constant sequence stays constant bit for bit
+            const double h0 = c0 + r0 / sw, h1 = c1 + r1 / sw, h2 = c2 + r2 / sw;
+            const double hv = sv / (sw * sw), hn = sn / sw;
+            if constexpr (kGather) {
+                o0 = h0, o1 = h1, o2 = h2, ov = hv, on = hn;
+            } else {
+                const double np1 = hn + 1.0;
+                on = np1 < a.max_history ? np1 : a.max_history;
+                const double al = 1.0 / on, be = 1.0 - al;
+                o0 = h0 + al * (c0 - h0);
+                o1 = h1 + al * (c1 - h1);
+                o2 = h2 + al * (c2 - h2);
+                ov = (al * al) * v + (be * be) * hv;
             }
         }
     }
@@ -532,6 +551,188 @@ hipError_t launch_rectify(const double* rgba, const double* se, const double* fe
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+// ---- Variance estimation (ptmi_variance_estimate) ----------------------------------------------
+// The standard error of this frame's pixels from the moments of each surface point's frames, accumulated
+// through reproject_pass's lookup (history_taps: one text, so the two cannot drift), and where that history is
+// shorter than min_temporal from a (2 kR + 1)^2 window of same-surface pixels of this frame.  Every FP64
+// operation is separately rounded and in the order ptmi/temporal.py variance_reference states.
+//
+// One thread per pixel on the 16 x 16 blocks, in three steps.
+//   1. Each pixel's own frame and record and its four temporal taps come from global memory, as in
+//      reproject_pass (200 B in, 72 B out per pixel), and give mu', mu2', N'.
+//   2. Only a pixel with N' < min_temporal needs the window.  The waves' ballots meet in LDS, and a block none
+//      of whose pixels needs it stages nothing and is done: from frame min_temporal on that is almost every
+//      block, and the pass costs what the gather costs.  Staging decides no value, so skipping it cannot
+//      change one.
+//   3. Otherwise the block and its halo of kR are staged as seven planes of doubles -- colour x 3, id,
+//      normal x 3 -- and the pixels that need it walk their taps from there; a wave none of whose lanes needs
+//      the window branches over the loop (the lanes' `need` is its exec mask).  An entry outside the image or
+//      whose colour is not finite is staged with id = NaN, which matches no id: of such an entry nothing else
+//      is written or used.
+// Layout: rectify_pass's -- rows of kRcPitch = 24 doubles in every plane, the wave's four rows to its 16-lane
+// groups in the order 0, 2, 1, 3.  Its argument does not depend on the number of planes, since one
+// ds_read_b64 reads one plane: within a 32-lane half the two rows are 48 doubles = 16 mod 32 apart, the two
+// runs of 16 doubles fill the 32 banks once, and no tap read conflicts at any kR or offset.  Seven planes at
+// kR = 4 are 24 x 24 x 7 x 8 B = 31.5 KB, five blocks per CU; at kR = 1, 23.6 KB.
+struct VrPlane {
+    enum { c0, c1, c2, id, n0, n1, n2, count };
+};
+template <bool kMotion, int kR>
+__global__ __launch_bounds__(kDnX * kDnY) void variance_pass(const double* __restrict__ rgba,
+                                                               const double* __restrict__ se,
+                                                               const double* __restrict__ feat,
+                                                               const double* __restrict__ prev_mom,
+                                                               const double* __restrict__ prev_feat, VarianceArgs a,
+                                                               double* __restrict__ out_mom,
+                                                               double* __restrict__ out_se,
+                                                               const double* __restrict__ motion, int n_obj) {
+    constexpr int kTW = kDnX + 2 * kR, kTH = kDnY + 2 * kR;
+    static_assert(kTW <= kRcPitch, "a tile row fits the pitch");
+    __shared__ double lds[VrPlane::count][kTH * kRcPitch];
+    __shared__ uint32_t wave_need[kDnX * kDnY / 64];
+    const int W = a.r.W, H = a.r.H;
+    const int bx0 = (int)blockIdx.x * kDnX, by0 = (int)blockIdx.y * kDnY;
+    // rows 0, 2, 1, 3 of the wave's four to its 16-lane groups (the layout note above)
+    const int lane = (int)threadIdx.x & 63, grp = lane >> 4;
+    const int lx = lane & 15, ly = ((int)threadIdx.x >> 6) * 4 + (((grp & 1) << 1) | (grp >> 1));
+    const int x = bx0 + lx, y = by0 + ly;
+    const bool inside = x < W && y < H;
+    const size_t i = inside ? (size_t)y * W + x : 0;
+    double c0 = 0.0, c1 = 0.0, c2 = 0.0, s = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0, id = 0.0;
+    double o0 = 0.0, o1 = 0.0, o2 = 0.0, o3 = 0.0, on = 0.0, src = 0.0, var = 0.0;
+    bool fin = false, need = false;
+    if (inside) {
+        const double2* p = reinterpret_cast<const double2*>(rgba + 4 * i);
+        const double2* f = reinterpret_cast<const double2*>(feat + 12 * i);
+        const double2 p0 = p[0], p1 = p[1], f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
+        c0 = p0.x, c1 = p0.y, c2 = p1.x;
+        n0 = f2.x, n1 = f2.y, n2 = f3.x, id = f3.y;
+        s = (c0 * c0 + c1 * c1) + c2 * c2;
+        fin = isfinite(c0) && isfinite(c1) && isfinite(c2);
+        // the reset: this frame alone (a pixel that is not finite is no history for the next frame)
+        o0 = c0, o1 = c1, o2 = c2, o3 = s, on = fin ? 1.0 : 0.0;
+        if (prev_mom != nullptr && fin && !(id < 0.0)) {
+            double sw = 0.0, r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, sn = 0.0;
+            history_taps<kMotion>(a.r, prev_mom, prev_feat, motion, n_obj, f0.x, f0.y, f1.x, f1.y, n0, n1, n2, id,
+                                  [&](double w, const double2& h0, const double2& h1, const double2& h2) {
+                                      sw = sw + w;
+                                      r0 = r0 + w * (h0.x - c0);
+                                      r1 = r1 + w * (h0.y - c1);
+                                      r2 = r2 + w * (h1.x - c2);
+                                      r3 = r3 + w * (h1.y - s);
+                                      sn = sn + w * h2.x;
+                                  });
+            if (sw >= a.r.min_weight && sw > 0.0) {
+                // plain weighted means written around c and s, and the blend around them: a constant sequence
+                // keeps mu' = c and mu2' = s bit for bit
+                const double h0 = c0 + r0 / sw, h1 = c1 + r1 / sw, h2 = c2 + r2 / sw, h3 = s + r3 / sw;
+                const double np1 = sn / sw + 1.0;
+                on = np1 < a.r.max_history ? np1 : a.r.max_history;
+                const double al = 1.0 / on;
+                o0 = h0 + al * (c0 - h0);
+                o1 = h1 + al * (c1 - h1);
+                o2 = h2 + al * (c2 - h2);
+                o3 = h3 + al * (s - h3);
+            }
+        }
+        if (fin) {
+            if (on >= a.min_temporal) {
+                const double d = o3 - ((o0 * o0 + o1 * o1) + o2 * o2);
+                var = (d < 0.0 ? 0.0 : d) * (on / (on - 1.0));
+                src = 1.0;
+            } else {
+                need = true;
+            }
+        }
+    }
+    // does a pixel of the block need the window?
+    const unsigned long long wave_mask = __ballot(need);
+    if (lane == 0) wave_need[threadIdx.x >> 6] = wave_mask != 0ull ? 1u : 0u;
+    __syncthreads();
+    if ((wave_need[0] | wave_need[1]) | (wave_need[2] | wave_need[3])) {  // (block-uniform)
+        for (int k = (int)threadIdx.x; k < kTW * kTH; k += kDnX * kDnY) {
+            const int tx = k % kTW, ty = k / kTW, e = ty * kRcPitch + tx;
+            const int qx = bx0 - kR + tx, qy = by0 - kR + ty;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) {
+                lds[VrPlane::id][e] = __builtin_nan("");
+                continue;
+            }
+            const size_t q = (size_t)qy * W + qx;
+            const double2* p = reinterpret_cast<const double2*>(rgba + 4 * q);
+            const double2* f = reinterpret_cast<const double2*>(feat + 12 * q);
+            const double2 p0 = p[0], p1 = p[1], f2 = f[2], f3 = f[3];
+            lds[VrPlane::c0][e] = p0.x, lds[VrPlane::c1][e] = p0.y, lds[VrPlane::c2][e] = p1.x;
+            lds[VrPlane::n0][e] = f2.x, lds[VrPlane::n1][e] = f2.y, lds[VrPlane::n2][e] = f3.x;
+            lds[VrPlane::id][e] = isfinite(p0.x) && isfinite(p0.y) && isfinite(p1.x) ? f3.y : __builtin_nan("");
+        }
+        __syncthreads();
+        if (need) {
+            const int ce = (ly + kR) * kRcPitch + (lx + kR);
+            const bool hit = !(id < 0.0);
+            uint32_t m = 0;
+            double e0 = 0.0, e1 = 0.0, e2 = 0.0, b = 0.0;
+            for (int dy = -kR; dy <= kR; dy++) {
+#pragma unroll
+                for (int dx = -kR; dx <= kR; dx++) {
+                    const int e = ce + dy * kRcPitch + dx;
+                    if (lds[VrPlane::id][e] != id) continue;  // (a NaN id matches nothing; misses match misses)
+                    if (hit) {
+                        const double dn = (n0 * lds[VrPlane::n0][e] + n1 * lds[VrPlane::n1][e]) + n2 * lds[VrPlane::n2][e];
+                        if (!(dn >= a.window_normal_cos)) continue;
+                    }
+                    const double d0 = lds[VrPlane::c0][e] - c0, d1 = lds[VrPlane::c1][e] - c1, d2 = lds[VrPlane::c2][e] - c2;
+                    m = m + 1;
+                    e0 = e0 + d0;
+                    e1 = e1 + d1;
+                    e2 = e2 + d2;
+                    b = b + ((d0 * d0 + d1 * d1) + d2 * d2);
+                }
+            }
+            if (m >= a.min_count) {
+                const double md = (double)m;
+                const double g0 = e0 / md, g1 = e1 / md, g2 = e2 / md;
+                const double d = b / md - ((g0 * g0 + g1 * g1) + g2 * g2);
+                var = (d < 0.0 ? 0.0 : d) * (md / (md - 1.0));
+                src = 2.0;
+            } else {  // the pixel's own magnitude, unless the frame's samples gave a standard error
+                const double sp = se ? se[i] : __builtin_inf();
+                var = isfinite(sp) ? sp * sp : s;
+                src = 3.0;
+            }
+        }
+    }
+    if (!inside) return;
+    double2* om = reinterpret_cast<double2*>(out_mom + 8 * i);
+    om[0] = make_double2(o0, o1);
+    om[1] = make_double2(o2, o3);
+    om[2] = make_double2(on, src);
+    om[3] = make_double2(var, 0.0);
+    out_se[i] = fin ? sqrt(var) : se ? se[i] : __builtin_inf();
+}
+
+template <bool kMotion>
+static hipError_t launch_variance_r(const double* rgba, const double* se, const double* feat, const double* prev_mom,
+                                    const double* prev_feat, const VarianceArgs& a, uint32_t radius, double* out_mom,
+                                    double* out_se, const double* motion, int n_obj, hipStream_t st) {
+    const dim3 grid(((uint32_t)a.r.W + kDnX - 1) / kDnX, ((uint32_t)a.r.H + kDnY - 1) / kDnY), block(kDnX * kDnY);
+    switch (radius) {
+        case 1: hipLaunchKernelGGL((variance_pass<kMotion, 1>), grid, block, 0, st, rgba, se, feat, prev_mom, prev_feat, a, out_mom, out_se, motion, n_obj); break;
+        case 2: hipLaunchKernelGGL((variance_pass<kMotion, 2>), grid, block, 0, st, rgba, se, feat, prev_mom, prev_feat, a, out_mom, out_se, motion, n_obj); break;
+        case 3: hipLaunchKernelGGL((variance_pass<kMotion, 3>), grid, block, 0, st, rgba, se, feat, prev_mom, prev_feat, a, out_mom, out_se, motion, n_obj); break;
+        case 4: hipLaunchKernelGGL((variance_pass<kMotion, 4>), grid, block, 0, st, rgba, se, feat, prev_mom, prev_feat, a, out_mom, out_se, motion, n_obj); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_variance(const double* rgba, const double* se, const double* feat, const double* prev_mom,
+                           const double* prev_feat, const VarianceArgs& a, uint32_t radius, double* out_mom,
+                           double* out_se, const double* motion, int32_t n_obj, hipStream_t st) {
+    if (motion)
+        return launch_variance_r<true>(rgba, se, feat, prev_mom, prev_feat, a, radius, out_mom, out_se, motion, (int)n_obj, st);
+    return launch_variance_r<false>(rgba, se, feat, prev_mom, prev_feat, a, radius, out_mom, out_se, nullptr, 0, st);
 }
 
 // ---- error map and accumulate (ptmi_error_map, ptmi_accumulate) ------------------------------

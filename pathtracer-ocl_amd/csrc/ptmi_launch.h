@@ -55,6 +55,9 @@ hipError_t launch_history_gather(const double* rgba, const double* se, const dou
 hipError_t launch_rectify(const double* rgba, const double* se, const double* feat, const double* gathered,
                           const RectifyArgs& a, uint32_t radius, double* out_hist, double* out_rgba, double* out_se,
                           hipStream_t st);
+hipError_t launch_variance(const double* rgba, const double* se, const double* feat, const double* prev_mom,
+                           const double* prev_feat, const VarianceArgs& a, uint32_t radius, double* out_mom,
+                           double* out_se, const double* motion, int32_t n_obj, hipStream_t st);
 hipError_t launch_error_map(const double* sums, const double* sq, uint32_t W, uint32_t H, double* se, double* tile_err,
                             double* tile_part, double* stats, hipStream_t st);
 hipError_t launch_accumulate(double* dst, const double* src, size_t n, hipStream_t st);

@@ -42,6 +42,11 @@
 // frame before it is blended (ptmi_history_gather, ptmi_rectify; --rectify-gamma G, default 3, and
 // --rectify-radius R, 1..4, default 3), and --emission-step F multiplies the emission of every emissive object
 // by F from frame N / 2 on (ptmi_scene_set_objects): a lighting change from the command line.
+// --estimate-variance (with --temporal) estimates each frame's standard error from the moments of each surface
+// point's frames and, where that history is short, from a window of same-surface pixels (ptmi_variance_estimate on
+// a moment history of its own; --var-min-history N, 2..65536, default 4, and --var-radius R, 1..4, default 3), and
+// the accumulation, --rectify and --denoise take that map in the place of the rendered one: --samples 1 is then a
+// normal input.
 // An unknown --scene renders the OCL scene, as main.go:86-88 does.
 #include <algorithm>
 #include <chrono>
@@ -89,6 +94,8 @@ struct Cfg {
     std::string guides = "first";
     int max_chain = 8;
     bool have_guides = false, have_chain = false;
+    bool estimate_variance = false, have_var_history = false, have_var_radius = false;
+    int var_min_history = 4, var_radius = 3;
 };
 
 // The guide records of the scene's camera: the first hits, or with --guides specular the chains' final surfaces.
@@ -106,7 +113,8 @@ int trace_guides(const Cfg& c, ptmi_scene* sc, double* feat, char* err, size_t e
                  "          [--adaptive] [--sample-map FILE.raw] [--denoise] [--denoise-iters N]\n"
                  "          [--features FILE.raw] [--frames N] [--orbit-step DEGREES] [--temporal] [--max-history N]\n"
                  "          [--move-object I --move-step DX,DY,DZ] [--rectify] [--rectify-gamma G] [--rectify-radius R]\n"
-                 "          [--emission-step F] [--guides first|specular] [--max-chain N]\n",
+                 "          [--emission-step F] [--guides first|specular] [--max-chain N]\n"
+                 "          [--estimate-variance] [--var-min-history N] [--var-radius R]\n",
                  msg);
     std::exit(2);
 }
@@ -166,6 +174,9 @@ Cfg parse(int argc, char** argv) {
         else if (a == "--emission-step") c.emission_step = std::atof(val().c_str()), c.have_emission = true;
         else if (a == "--guides") c.guides = val(), c.have_guides = true;
         else if (a == "--max-chain") c.max_chain = std::atoi(val().c_str()), c.have_chain = true;
+        else if (a == "--estimate-variance") c.estimate_variance = true;
+        else if (a == "--var-min-history") c.var_min_history = std::atoi(val().c_str()), c.have_var_history = true;
+        else if (a == "--var-radius") c.var_radius = std::atoi(val().c_str()), c.have_var_radius = true;
         else if (a == "--help" || a == "-h") usage("pt: path tracer on AMD Instinct GPUs");
         else usage(("unknown flag " + a).c_str());
     }
@@ -200,7 +211,13 @@ Cfg parse(int argc, char** argv) {
     if (c.have_radius && (c.rectify_radius < 1 || c.rectify_radius > 4)) usage("--rectify-radius must be 1..4");
     if (c.have_emission && !sequence) usage("--emission-step needs --frames N with N > 1");
     if (c.have_emission && !(std::isfinite(c.emission_step) && c.emission_step >= 0.0)) usage("--emission-step must be finite and >= 0");
-    if (c.temporal && c.samples < 2) usage("--temporal needs --samples >= 2 (the variance of a frame)");
+    if (c.estimate_variance && !c.temporal) usage("--estimate-variance needs --temporal");
+    if ((c.have_var_history || c.have_var_radius) && !c.estimate_variance)
+        usage("--var-min-history and --var-radius need --estimate-variance");
+    if (c.have_var_history && (c.var_min_history < 2 || c.var_min_history > 65536)) usage("--var-min-history must be 2..65536");
+    if (c.have_var_radius && (c.var_radius < 1 || c.var_radius > 4)) usage("--var-radius must be 1..4");
+    if (c.temporal && c.samples < 2 && !c.estimate_variance)
+        usage("--temporal needs --samples >= 2 (the variance of a frame)");
     if (c.guides != "first" && c.guides != "specular") usage("--guides first|specular");
     if (c.have_guides && !(c.denoise || c.temporal || !c.features.empty()))
         usage("--guides needs --denoise, --temporal or --features");
@@ -384,8 +401,8 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
     if (rc) return rc;
     double *seeds = nullptr, *sums = nullptr, *sq = nullptr, *se = nullptr, *stats = nullptr, *image = nullptr,
            *acc = nullptr, *acc_se = nullptr, *dn_out = nullptr, *dn_se = nullptr, *dn_work = nullptr, *motion = nullptr,
-           *gathered = nullptr;
-    double *feat[2] = {nullptr, nullptr}, *hist[2] = {nullptr, nullptr};
+           *gathered = nullptr, *se_est = nullptr;
+    double *feat[2] = {nullptr, nullptr}, *hist[2] = {nullptr, nullptr}, *mom[2] = {nullptr, nullptr};
     auto hip = [&](hipError_t e, const char* what) {
         if (e == hipSuccess) return false;
         std::snprintf(err, err_len, "%s failed: %s", what, hipGetErrorString(e));
@@ -422,6 +439,9 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             break;
         if (moving && c.temporal && dmalloc(&motion, (size_t)PTMI_MOTION_DOUBLES * PTMI_MAX_OBJECTS)) break;
         if (c.rectify && dmalloc(&gathered, n * PTMI_HISTORY_DOUBLES)) break;
+        if (c.estimate_variance &&
+            (dmalloc(&mom[0], n * PTMI_MOMENT_DOUBLES) || dmalloc(&mom[1], n * PTMI_MOMENT_DOUBLES) || dmalloc(&se_est, n)))
+            break;
         for (int k = 0; k < c.frames && !rc; k++) {
             if (moving) {
                 prev_objs = objs;
@@ -463,18 +483,29 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
                 if (c.max_history) rp.max_history = (uint32_t)c.max_history;
                 if (moving && k && (rc = ptmi_motion_table(prev_objs.data(), objs.data(), r.n_obj, motion, nullptr, err, err_len)))
                     break;
+                const double* se_in = se;  // the standard error the accumulation and the filter take
+                if (c.estimate_variance) {
+                    ptmi_variance_params vp{rp.max_history, (uint32_t)c.var_min_history, (uint32_t)c.var_radius, 9, 0,
+                                            rp.normal_cos, rp.plane_dist, rp.min_weight, 0.9};
+                    if ((rc = ptmi_variance_estimate(image, se, f, k ? mom[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
+                                                     k ? prev_cam : nullptr, W, H, &vp, mom[k & 1], se_est,
+                                                     moving && k ? motion : nullptr, moving && k ? r.n_obj : 0, nullptr, err,
+                                                     err_len)))
+                        break;
+                    se_in = se_est;
+                }
                 if (c.rectify) {
                     ptmi_rectify_params tp{(uint32_t)c.rectify_radius, 9, c.rectify_gamma, rp.max_history, 0};
-                    if ((rc = ptmi_history_gather(image, se, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
+                    if ((rc = ptmi_history_gather(image, se_in, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
                                                   k ? prev_cam : nullptr, W, H, &rp, gathered, moving && k ? motion : nullptr,
                                                   moving && k ? r.n_obj : 0, nullptr, err, err_len)))
                         break;
-                    rc = ptmi_rectify(image, se, f, gathered, W, H, &tp, hist[k & 1], acc, acc_se, nullptr, err, err_len);
+                    rc = ptmi_rectify(image, se_in, f, gathered, W, H, &tp, hist[k & 1], acc, acc_se, nullptr, err, err_len);
                 } else if (moving && k) {
-                    rc = ptmi_reproject_motion(image, se, f, hist[(k - 1) & 1], feat[(k - 1) & 1], prev_cam, W, H, &rp,
+                    rc = ptmi_reproject_motion(image, se_in, f, hist[(k - 1) & 1], feat[(k - 1) & 1], prev_cam, W, H, &rp,
                                                hist[k & 1], acc, acc_se, motion, r.n_obj, nullptr, err, err_len);
                 } else {
-                    rc = ptmi_reproject(image, se, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
+                    rc = ptmi_reproject(image, se_in, f, k ? hist[(k - 1) & 1] : nullptr, k ? feat[(k - 1) & 1] : nullptr,
                                         k ? prev_cam : nullptr, W, H, &rp, hist[k & 1], acc, acc_se, nullptr, err, err_len);
                 }
                 if (rc) break;
@@ -495,8 +526,8 @@ int render_frames(const Cfg& c, const ptmi_records& r, const ptmi_textures* tex,
             std::fprintf(stderr, "frame %d (%.6g degrees): wrote %s\n", k, (double)k * c.orbit_step, name.c_str());
         }
     } while (false);
-    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, motion, gathered, feat[0], feat[1],
-                      hist[0], hist[1]})
+    for (double* p : {seeds, sums, sq, se, stats, image, acc, acc_se, dn_out, dn_se, dn_work, motion, gathered, se_est, feat[0],
+                      feat[1], hist[0], hist[1], mom[0], mom[1]})
         if (p) (void)hipFree(p);
     ptmi_scene_destroy(sc);
     return rc;

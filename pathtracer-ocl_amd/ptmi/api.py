@@ -41,10 +41,11 @@ EXPORTS = ("ptmi_trace", "ptmi_device_count", "ptmi_device_name", "ptmi_scene_cr
            "ptmi_scene_render_tiles", "ptmi_select_tiles", "ptmi_finalize_counts", "ptmi_scene_features",
            "ptmi_denoise", "ptmi_denoise_work_bytes", "ptmi_scene_set_camera", "ptmi_reproject",
            "ptmi_scene_set_objects", "ptmi_motion_table", "ptmi_reproject_motion", "ptmi_history_gather",
-           "ptmi_rectify", "ptmi_scene_features_chain")
+           "ptmi_rectify", "ptmi_scene_features_chain", "ptmi_variance_estimate")
 FEATURE_DOUBLES = 12    # PTMI_FEATURE_DOUBLES: doubles per pixel of Scene.features
 HISTORY_DOUBLES = 8     # PTMI_HISTORY_DOUBLES: doubles per pixel of a reproject history
 MOTION_DOUBLES = 24     # PTMI_MOTION_DOUBLES: doubles per object of a motion table
+MOMENT_DOUBLES = 8      # PTMI_MOMENT_DOUBLES: doubles per pixel of a variance_estimate moment record
 DENOISE_DEMODULATE = 1  # PTMI_DENOISE_DEMODULATE
 
 
@@ -82,6 +83,18 @@ class RectifyParams(ctypes.Structure):
 
     def __init__(self, radius=3, min_count=9, gamma=3.0, max_history=32, flags=0):
         super().__init__(radius, min_count, gamma, max_history, flags)
+
+
+class VarianceParams(ctypes.Structure):
+    """ptmi_variance_params (include/ptmi.h); the constructor's defaults are the library's."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("min_temporal", ctypes.c_uint32), ("radius", ctypes.c_uint32),
+                ("min_count", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("normal_cos", ctypes.c_double),
+                ("plane_dist", ctypes.c_double), ("min_weight", ctypes.c_double), ("window_normal_cos", ctypes.c_double)]
+
+    def __init__(self, max_history=32, min_temporal=4, radius=3, min_count=9, flags=0, normal_cos=0.9, plane_dist=0.02,
+                 min_weight=0.05, window_normal_cos=0.9):
+        super().__init__(max_history, min_temporal, radius, min_count, flags, normal_cos, plane_dist, min_weight,
+                         window_normal_cos)
 
 
 class PtmiError(RuntimeError):
@@ -176,6 +189,10 @@ def load_library(path=None):
                                             u32, vp, cp, sz]
         lib.ptmi_rectify.restype = i32
         lib.ptmi_rectify.argtypes = [vp, vp, vp, vp, u32, u32, ctypes.POINTER(RectifyParams), vp, vp, vp, vp, cp, sz]
+    if hasattr(lib, "ptmi_variance_estimate"):  # (likewise)
+        lib.ptmi_variance_estimate.restype = i32
+        lib.ptmi_variance_estimate.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(VarianceParams), vp, vp,
+                                               vp, u32, vp, cp, sz]
     if hasattr(lib, "ptmi_diag_scene_tile_cost"):
         lib.ptmi_diag_scene_tile_cost.restype = i32
         lib.ptmi_diag_scene_tile_cost.argtypes = [vp, vp, u32, cp, sz]
@@ -765,3 +782,31 @@ def rectify(rgba_ptr, se_ptr, feat_ptr, gathered_ptr, w, h, out_hist_ptr, out_rg
         ctypes.c_void_p(gathered_ptr or None), int(w), int(h), ctypes.byref(p) if p is not None else None,
         ctypes.c_void_p(out_hist_ptr or None), ctypes.c_void_p(out_rgba_ptr or None),
         ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(stream), err, len(err)), err)
+
+
+def variance_params(params=None):
+    """A VarianceParams from None (the defaults), a VarianceParams or a dict of some of its fields."""
+    if params is None or isinstance(params, VarianceParams):
+        return params
+    return VarianceParams(**dict(params))
+
+
+def variance_estimate(rgba_ptr, se_ptr, feat_ptr, prev_mom_ptr, prev_feat_ptr, prev_camera, w, h, out_mom_ptr,
+                      out_se_ptr, motion_ptr=0, n_obj=0, params=None, stream=0):
+    """ptmi_variance_estimate: the standard error of a W x H frame's pixels estimated from the moments of each
+    surface point's frames -- accumulated through history_gather()'s lookup (with motion_ptr and n_obj,
+    reproject_motion()'s) on the previous frame's moment record (prev_mom_ptr, W*H*MOMENT_DOUBLES; 0 = first
+    frame) -- or, where that history is too short, from a window of same-surface pixels of this frame.
+    out_mom_ptr gets (mu', mu2', N', source, var, 0) per pixel and out_se_ptr sqrt(var), which reproject(),
+    history_gather() + rectify() and denoise() take in the place of error_map()'s se; se_ptr (the map as
+    rendered) may be 0.  params: None, a VarianceParams or a dict of its fields.  The operation order is
+    ptmi/temporal.py variance_reference."""
+    p = variance_params(params)
+    cam = _camera_record(prev_camera)
+    err = ctypes.create_string_buffer(512)
+    _check(load_library().ptmi_variance_estimate(
+        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
+        ctypes.c_void_p(prev_mom_ptr or None), ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
+        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_mom_ptr or None),
+        ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(motion_ptr or None), int(n_obj), ctypes.c_void_p(stream),
+        err, len(err)), err)

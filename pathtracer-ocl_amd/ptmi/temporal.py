@@ -21,9 +21,13 @@ geometry inside a mesh does not deform.  ``gather_reference`` and ``rectify_refe
 ptmi_history_gather and ptmi_rectify (``render_sequence(rectify=...)``), which test the history found
 against the frame over a window of same-object pixels and so bound that lag; they see a change of the
 window's mean only, test no window of fewer than min_count such pixels, and take the window's pixels for
-independent.  The variance needs at least 2 spp per frame (at
-1 spp the standard error is +inf and every pixel resets), and it takes the frames for independent
-estimates: render them with different seeds.  One GPU.
+independent.  The rendered variance needs at least 2 spp per frame (at 1 spp the standard error is +inf and every
+pixel resets), and it takes the frames for independent estimates: render them with different seeds.
+``variance_reference`` restates ptmi_variance_estimate (``render_sequence(variance="estimated")``), which
+estimates each frame's standard error from the moments of each surface point's frames or, where that history is
+short, from a window of same-surface pixels: 1 spp is then a normal input.  Both estimates take real changes
+(view-dependent shading, moving lights; shading gradients and texture inside the window) for noise and then
+overestimate, and the moment history is not rectified.  One GPU.
 """
 import math
 
@@ -176,6 +180,59 @@ def gather_reference(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, pa
     return (res[0], res[3]) if details else res[0]
 
 
+def _history_taps(cand, x, t, n, oid, ph, pf, cam, w, h, p, motion, n_obj):
+    """The lookup that ``_reproject`` and ``variance_reference`` share (the device's history_taps): the
+    candidates' points carried back by `motion`, projected with the previous camera `cam`, and the four taps
+    tested.  ph[h*w, 8] is the previous frame's per-pixel record -- a history or a moment record: slots
+    [0:4] must be finite and [4] > 0 for a tap to be usable -- and pf its first-hit records.  Returns
+    (front, taps, info): per tap of TAPS a dict(ok=, wt=, rec= the tap's record [h, w, 8], usable=, dn=, dd=),
+    and the decisions' test quantities but W and blend, which are the caller's."""
+    if int(cam["width"]) != w or int(cam["height"]) != h:
+        raise ValueError("prev_camera is %dx%d, the frame %dx%d" % (cam["width"], cam["height"], w, h))
+    T = cofactor_inverse(cam["inverse"])
+    hw, hh, ps = float(cam["half_width"]), float(cam["half_height"]), float(cam["pixel_size"])
+    history = np.ones((h, w), dtype=bool)
+    if motion is not None:  # the point and its normal as the previous frame saw them
+        mt = np.asarray(motion, dtype=np.float64).reshape(-1, MOTION_DOUBLES)[:int(n_obj)]
+        known = cand & (oid < float(n_obj))
+        rec = mt[np.where(known, oid, 0.0).astype(np.int64)]
+        moved = known & (rec[..., M_STATE] == MOTION_MOVED)
+        history = ~(known & (rec[..., M_STATE] != MOTION_MOVED) & (rec[..., M_STATE] != MOTION_STATIC))
+        xm = [((rec[..., 4 * k] * x[..., 0] + rec[..., 4 * k + 1] * x[..., 1]) + rec[..., 4 * k + 2] * x[..., 2]) +
+              rec[..., 4 * k + 3] for k in range(3)]
+        e = [(rec[..., 12 + 3 * k] * n[..., 0] + rec[..., 13 + 3 * k] * n[..., 1]) + rec[..., 14 + 3 * k] * n[..., 2]
+             for k in range(3)]
+        ln = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]
+        history &= ~(moved & ~((ln > 0.0) & np.isfinite(ln)))
+        root = np.sqrt(ln)
+        x = np.where(moved[..., None], np.stack(xm, -1), x)
+        n = np.where(moved[..., None], np.stack([e[0] / root, e[1] / root, e[2] / root], -1), n)
+    q = [((T[4 * k] * x[..., 0] + T[4 * k + 1] * x[..., 1]) + T[4 * k + 2] * x[..., 2]) + T[4 * k + 3]
+         for k in range(3)]
+    z = -q[2]
+    front = cand & history & (z > 0.0)
+    fu = (hw - q[0] / z) / ps - 0.5
+    fv = (hh - q[1] / z) / ps - 0.5
+    x0, y0 = np.floor(fu), np.floor(fv)
+    wx, wy = fu - x0, fv - y0
+    bound = p["plane_dist"] * t
+    taps = []
+    for i, j in TAPS:
+        tx, ty = x0 + i, y0 + j
+        inside = (tx >= 0.0) & (tx < w) & (ty >= 0.0) & (ty < h)
+        qi = np.where(inside, ty, 0.0).astype(np.int64) * w + np.where(inside, tx, 0.0).astype(np.int64)
+        rq = ph[qi]
+        xq, nq, idq = pf[qi][..., F_POS], pf[qi][..., F_NRM], pf[qi][..., F_ID]
+        usable = inside & (rq[..., H_N] > 0.0) & _finite4(rq[..., H_COL], rq[..., H_VAR]) & (idq == oid)
+        dn = (n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2]
+        dd = (n[..., 0] * (xq[..., 0] - x[..., 0]) + n[..., 1] * (xq[..., 1] - x[..., 1])) + \
+            n[..., 2] * (xq[..., 2] - x[..., 2])
+        ok = front & usable & (dn >= p["normal_cos"]) & (np.abs(dd) <= bound)
+        wt = (wx if i else 1.0 - wx) * (wy if j else 1.0 - wy)
+        taps.append(dict(ok=ok, wt=wt, rec=rq, usable=front & usable, dn=dn, dd=np.abs(dd)))
+    return front, taps, dict(candidate=cand, front=front, z=z, t=t, fu=fu, fv=fv, bound=bound, taps=taps)
+
+
 def _reproject(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params, details, motion, n_obj, gather):
     """The body of reproject_reference (gather=False) and gather_reference (gather=True)."""
     p = params_dict(params)
@@ -193,56 +250,18 @@ def _reproject(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params, 
             ph = np.asarray(prev_hist, dtype=np.float64).reshape(h * w, HISTORY_DOUBLES)
             pf = np.asarray(prev_feat, dtype=np.float64).reshape(h * w, FEATURE_DOUBLES)
             cam = np.asarray(prev_camera).reshape(1)[0]
-            if int(cam["width"]) != w or int(cam["height"]) != h:
-                raise ValueError("prev_camera is %dx%d, the frame %dx%d" % (cam["width"], cam["height"], w, h))
-            T = cofactor_inverse(cam["inverse"])
-            hw, hh, ps = float(cam["half_width"]), float(cam["half_height"]), float(cam["pixel_size"])
             cand = fin & ~(oid < 0.0)
-            history = np.ones((h, w), dtype=bool)
-            if motion is not None:  # the point and its normal as the previous frame saw them
-                mt = np.asarray(motion, dtype=np.float64).reshape(-1, MOTION_DOUBLES)[:int(n_obj)]
-                known = cand & (oid < float(n_obj))
-                rec = mt[np.where(known, oid, 0.0).astype(np.int64)]
-                moved = known & (rec[..., M_STATE] == MOTION_MOVED)
-                history = ~(known & (rec[..., M_STATE] != MOTION_MOVED) & (rec[..., M_STATE] != MOTION_STATIC))
-                xm = [((rec[..., 4 * k] * x[..., 0] + rec[..., 4 * k + 1] * x[..., 1]) + rec[..., 4 * k + 2] * x[..., 2]) +
-                      rec[..., 4 * k + 3] for k in range(3)]
-                e = [(rec[..., 12 + 3 * k] * n[..., 0] + rec[..., 13 + 3 * k] * n[..., 1]) + rec[..., 14 + 3 * k] * n[..., 2]
-                     for k in range(3)]
-                ln = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]
-                history &= ~(moved & ~((ln > 0.0) & np.isfinite(ln)))
-                root = np.sqrt(ln)
-                x = np.where(moved[..., None], np.stack(xm, -1), x)
-                n = np.where(moved[..., None], np.stack([e[0] / root, e[1] / root, e[2] / root], -1), n)
-            q = [((T[4 * k] * x[..., 0] + T[4 * k + 1] * x[..., 1]) + T[4 * k + 2] * x[..., 2]) + T[4 * k + 3]
-                 for k in range(3)]
-            z = -q[2]
-            front = cand & history & (z > 0.0)
-            fu = (hw - q[0] / z) / ps - 0.5
-            fv = (hh - q[1] / z) / ps - 0.5
-            x0, y0 = np.floor(fu), np.floor(fv)
-            wx, wy = fu - x0, fv - y0
-            bound = p["plane_dist"] * t
+            front, taps, info = _history_taps(cand, x, t, n, oid, ph, pf, cam, w, h, p, motion, n_obj)
             sw, sv, sn, r = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 3))
-            taps = []
-            for i, j in TAPS:
-                tx, ty = x0 + i, y0 + j
-                inside = (tx >= 0.0) & (tx < w) & (ty >= 0.0) & (ty < h)
-                qi = np.where(inside, ty, 0.0).astype(np.int64) * w + np.where(inside, tx, 0.0).astype(np.int64)
-                cq, vq, nq_hist = ph[qi][..., H_COL], ph[qi][..., H_VAR], ph[qi][..., H_N]
-                xq, nq, idq = pf[qi][..., F_POS], pf[qi][..., F_NRM], pf[qi][..., F_ID]
-                usable = inside & (nq_hist > 0.0) & _finite4(cq, vq) & (idq == oid)
-                dn = (n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2]
-                dd = (n[..., 0] * (xq[..., 0] - x[..., 0]) + n[..., 1] * (xq[..., 1] - x[..., 1])) + \
-                    n[..., 2] * (xq[..., 2] - x[..., 2])
-                ok = front & usable & (dn >= p["normal_cos"]) & (np.abs(dd) <= bound)
-                wt = (wx if i else 1.0 - wx) * (wy if j else 1.0 - wy)
+            for tap in taps:
+                ok, wt = tap["ok"], tap["wt"]
+                cq, vq, nq_hist = tap["rec"][..., H_COL], tap["rec"][..., H_VAR], tap["rec"][..., H_N]
                 sw = np.where(ok, sw + wt, sw)
                 r = np.where(ok[..., None], r + wt[..., None] * (cq - c), r)
                 sv = np.where(ok, sv + (wt * wt) * vq, sv)
                 sn = np.where(ok, sn + wt * nq_hist, sn)
-                taps.append(dict(usable=front & usable, dn=dn, dd=np.abs(dd)))
             blend = front & (sw >= p["min_weight"]) & (sw > 0.0)
+            info.update(W=sw, blend=blend)
             h_c = c + r / sw[..., None]
             h_v, h_n = sv / (sw * sw), sn / sw
             np1 = h_n + 1.0
@@ -256,8 +275,6 @@ def _reproject(rgba, se, feat, prev_hist, prev_feat, prev_camera, w, h, params, 
             out_c = np.where(blend[..., None], c_new, out_c)
             out_v = np.where(blend, v_new, out_v)
             out_n = np.where(blend, n_new, out_n)
-            info = dict(candidate=cand, front=front, z=z, t=t, fu=fu, fv=fv, W=sw, bound=bound, taps=taps,
-                        blend=blend)
         hist = np.zeros((h, w, HISTORY_DOUBLES))
         hist[..., H_COL], hist[..., H_VAR], hist[..., H_N] = out_c, out_v, out_n
         out_rgba = np.ones((h, w, 4))
@@ -390,6 +407,155 @@ def rectify_reference(rgba, se, feat, gathered, w, h, params=None, details=False
     return res + (dict(m=m, d2=d2, T2=t2, rho=rho),) if details else res
 
 
+MOMENT_DOUBLES = 8  # PTMI_MOMENT_DOUBLES: mean colour[3], mean of (r^2 + g^2) + b^2, N, source, sigma^2, 0
+V_MEAN, V_SQ, V_N, V_SRC, V_VAR = slice(0, 3), 3, 4, 5, 6
+SRC_NONE, SRC_TEMPORAL, SRC_SPATIAL, SRC_FALLBACK = 0.0, 1.0, 2.0, 3.0
+VARIANCE_DEFAULTS = dict(max_history=32, min_temporal=4, radius=3, min_count=9, flags=0, normal_cos=0.9,
+                         plane_dist=0.02, min_weight=0.05, window_normal_cos=0.9)
+
+
+def variance_params_dict(params=None):
+    """The parameters as a dict with the defaults filled in (ptmi_variance_params): from None, a dict of some
+    fields, or an object with those attributes (api.VarianceParams)."""
+    p = dict(VARIANCE_DEFAULTS)
+    if params is not None:
+        for k in p:
+            if isinstance(params, dict):
+                if k in params:
+                    p[k] = params[k]
+            elif hasattr(params, k):
+                p[k] = getattr(params, k)
+    for k in ("max_history", "min_temporal", "radius", "min_count", "flags"):
+        p[k] = int(p[k])
+    for k in ("normal_cos", "plane_dist", "min_weight", "window_normal_cos"):
+        p[k] = float(p[k])
+        if not (np.isfinite(p[k]) and p[k] >= 0.0):
+            raise ValueError("bad variance parameters %r" % (p,))
+    if not (1 <= p["max_history"] <= 65536 and 2 <= p["min_temporal"] <= 65536 and 1 <= p["radius"] <= 4 and
+            2 <= p["min_count"] < 2 ** 32 and p["flags"] == 0):
+        raise ValueError("bad variance parameters %r" % (p,))
+    return p
+
+
+def variance_reference(rgba, se, feat, prev_mom, prev_feat, prev_camera, w, h, params=None, details=False, motion=None,
+                       n_obj=0):
+    """(mom[W*H*8], out_se[W*H]): the device kernel ptmi_variance_estimate, restated -- the standard error of
+    this frame's pixels estimated from the moments of each surface point's frames, or, where that history is
+    too short, from a window of same-surface pixels of this frame.  `se` (the map as rendered) may be None.
+
+    Per pixel p with colour c = rgba[p][:3], s = (c_r c_r + c_g c_g) + c_b c_b and record (x_p, t_p, n_p, id_p):
+      NOT FINITE  c not finite: mom = (c, s, N = 0, 0, 0, 0), out_se = se_p (+inf without `se`).
+      GATHER  ``reproject_reference``'s lookup on the previous frame's moment records (one body,
+              ``_history_taps``: the projection, the taps in its order, its acceptance tests and resets, with
+              `motion` its states); over the accepted taps, W += w and
+                r_k += w * (mu_q.k - c_k);  r2 += w * (mu2_q - s);  sn += w * N_q
+              h_mu = c + r / W,  h_mu2 = s + r2 / W,  h_N = sn / W  (plain weighted means, written around c and s).
+      BLEND   reset (no prev_mom, a miss, z <= 0, W < min_weight or W == 0, motion state 2): mu' = c, mu2' = s,
+              N' = 1.  Else N' = min(h_N + 1, max_history), a = 1 / N',
+              mu' = h_mu + a * (c - h_mu),  mu2' = h_mu2 + a * (s - h_mu2).
+      TEMPORAL  N' >= min_temporal:  d = mu2' - ((mu'_r mu'_r + mu'_g mu'_g) + mu'_b mu'_b),
+              var = (d < 0 ? 0 : d) * (N' / (N' - 1)),  source 1.
+      SPATIAL otherwise, over this frame: taps q = p + (dx, dy), dy outer, dx inner, both in [-radius, radius];
+              ACCEPTED when inside the image, c_q finite, id_q == id_p (a NaN id matches nothing; misses match
+              misses) and, unless id_p < 0,  (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= window_normal_cos.
+              In tap order, with D = c_q - c:  m += 1;  e_k += D_k;  b += (D_r D_r + D_g D_g) + D_b D_b.
+              m >= min_count:  E = e / m,  d = b / m - ((E_r E_r + E_g E_g) + E_b E_b),
+              var = (d < 0 ? 0 : d) * (m / (m - 1)),  source 2.
+      FALLBACK  else, source 3:  var = se_p * se_p when `se` is given and se_p is finite, else var = s.
+    mom = (mu', mu2', N', source, var, 0);  out_se = sqrt(var).
+
+    var estimates the variance of THIS frame's pixel value: sqrt(var) is what the consumers of se expect.
+    details=True also returns ``_history_taps``' dict with W and blend (``undecided``), walk (bool[H, W]: the
+    pixels that took the window) and window_gap (the smallest |n_p.n_q - window_normal_cos| over the taps that
+    the normal test alone decides, inf where there is none): ``variance_undecided``."""
+    p = variance_params_dict(params)
+    w, h, rad = int(w), int(h), p["radius"]
+    rgba = np.asarray(rgba, dtype=np.float64).reshape(h, w, 4)
+    se = None if se is None else np.asarray(se, dtype=np.float64).reshape(h, w)
+    feat = np.asarray(feat, dtype=np.float64).reshape(h, w, FEATURE_DOUBLES)
+    c, x, t, n, oid = rgba[..., :3], feat[..., F_POS], feat[..., F_T], feat[..., F_NRM], feat[..., F_ID]
+    with np.errstate(all="ignore"):
+        s = (c[..., 0] * c[..., 0] + c[..., 1] * c[..., 1]) + c[..., 2] * c[..., 2]
+        fin = np.isfinite(c).all(-1)
+        mu, mu2, n_new = c.copy(), s.copy(), np.where(fin, 1.0, 0.0)
+        info = dict(candidate=np.zeros((h, w), dtype=bool))
+        if prev_mom is not None:
+            ph = np.asarray(prev_mom, dtype=np.float64).reshape(h * w, MOMENT_DOUBLES)
+            pf = np.asarray(prev_feat, dtype=np.float64).reshape(h * w, FEATURE_DOUBLES)
+            cam = np.asarray(prev_camera).reshape(1)[0]
+            cand = fin & ~(oid < 0.0)
+            front, taps, info = _history_taps(cand, x, t, n, oid, ph, pf, cam, w, h, p, motion, n_obj)
+            sw, r2, sn, r = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, 3))
+            for tap in taps:
+                ok, wt = tap["ok"], tap["wt"]
+                sw = np.where(ok, sw + wt, sw)
+                r = np.where(ok[..., None], r + wt[..., None] * (tap["rec"][..., V_MEAN] - c), r)
+                r2 = np.where(ok, r2 + wt * (tap["rec"][..., V_SQ] - s), r2)
+                sn = np.where(ok, sn + wt * tap["rec"][..., V_N], sn)
+            blend = front & (sw >= p["min_weight"]) & (sw > 0.0)
+            info.update(W=sw, blend=blend)
+            h_mu = c + r / sw[..., None]
+            h_mu2, h_n = s + r2 / sw, sn / sw
+            np1 = h_n + 1.0
+            nb = np.where(np1 < float(p["max_history"]), np1, float(p["max_history"]))
+            a = 1.0 / nb
+            mu = np.where(blend[..., None], h_mu + a[..., None] * (c - h_mu), mu)
+            mu2 = np.where(blend, h_mu2 + a * (s - h_mu2), mu2)
+            n_new = np.where(blend, nb, n_new)
+        temporal = fin & (n_new >= float(p["min_temporal"]))
+        d = mu2 - ((mu[..., 0] * mu[..., 0] + mu[..., 1] * mu[..., 1]) + mu[..., 2] * mu[..., 2])
+        var_t = np.where(d < 0.0, 0.0, d) * (n_new / (n_new - 1.0))
+
+        def shifted(a, dx, dy, fill):
+            """a[y + dy, x + dx], `fill` outside the image."""
+            out = np.full(a.shape, fill, dtype=a.dtype)
+            ys, yd = slice(max(dy, 0), h + min(dy, 0)), slice(max(-dy, 0), h + min(-dy, 0))
+            xs, xd = slice(max(dx, 0), w + min(dx, 0)), slice(max(-dx, 0), w + min(-dx, 0))
+            out[yd, xd] = a[ys, xs]
+            return out
+
+        hit = ~(oid < 0.0)
+        m = np.zeros((h, w), dtype=np.int64)
+        e, b, gap = np.zeros((h, w, 3)), np.zeros((h, w)), np.full((h, w), np.inf)
+        for dy in range(-rad, rad + 1):
+            for dx in range(-rad, rad + 1):
+                same = shifted(fin, dx, dy, False) & (shifted(oid, dx, dy, np.nan) == oid)
+                nq = shifted(n, dx, dy, 0.0)
+                dot = (n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2]
+                ok = same & (~hit | (dot >= p["window_normal_cos"]))
+                dl = shifted(c, dx, dy, 0.0) - c
+                m = np.where(ok, m + 1, m)
+                e = np.where(ok[..., None], e + dl, e)
+                b = np.where(ok, b + ((dl[..., 0] * dl[..., 0] + dl[..., 1] * dl[..., 1]) + dl[..., 2] * dl[..., 2]), b)
+                gap = np.where(same & hit, np.minimum(gap, np.abs(dot - p["window_normal_cos"])), gap)
+        md = m.astype(np.float64)
+        eb = e / md[..., None]
+        ds = b / md - ((eb[..., 0] * eb[..., 0] + eb[..., 1] * eb[..., 1]) + eb[..., 2] * eb[..., 2])
+        var_s = np.where(ds < 0.0, 0.0, ds) * (md / (md - 1.0))
+        walk = fin & ~temporal
+        spatial = walk & (m >= p["min_count"])
+        fallback = walk & ~spatial
+        var_f = s if se is None else np.where(np.isfinite(se), se * se, s)
+        var = np.where(temporal, var_t, np.where(spatial, var_s, np.where(fallback, var_f, 0.0)))
+        mom = np.zeros((h, w, MOMENT_DOUBLES))
+        mom[..., V_MEAN], mom[..., V_SQ], mom[..., V_N] = mu, mu2, n_new
+        mom[..., V_SRC] = np.where(temporal, SRC_TEMPORAL, np.where(spatial, SRC_SPATIAL,
+                                                                    np.where(fallback, SRC_FALLBACK, SRC_NONE)))
+        mom[..., V_VAR] = var
+        out_se = np.where(fin, np.sqrt(var), np.inf if se is None else se)
+        info.update(walk=walk, window_gap=gap)
+    res = (mom.reshape(-1), out_se.reshape(-1))
+    return res + (info,) if details else res
+
+
+def variance_undecided(info, w, h, params=None, rtol=1e-9):
+    """``undecided`` for ``variance_reference(..., details=True)``: its lookup's decisions, and for a pixel that
+    took the window a tap's n_p.n_q within `rtol` relative of window_normal_cos."""
+    p = variance_params_dict(params)
+    out = undecided(info, w, h, p, rtol)
+    return out | (info["walk"] & (info["window_gap"] <= rtol * p["window_normal_cos"]))
+
+
 def orbit_camera(camera_record, degrees):
     """A copy of the camera record whose inverse is rotate_y(degrees) * inverse: the camera orbits about
     the world y axis through the origin (CLCamera carries no from / to to rebuild a view from).  The
@@ -416,7 +582,8 @@ def move_object(objects, index, matrix):
 
 
 def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise=False, reproject_params=None,
-                    denoise_params=None, chunks=0, stream=None, objects=None, rectify=None, guides="first"):
+                    denoise_params=None, chunks=0, stream=None, objects=None, rectify=None, guides="first",
+                    variance="rendered", variance_params=None):
     """Render one frame per camera record of `cameras` from the resident `scene` (api.Scene), per frame k:
     set_camera, fill_seeds(seed_stream + k), render_moments, error_map, finalize, features, and with
     `temporal` reproject against frame k - 1, with `denoise` the a-trous filter on the result.
@@ -436,6 +603,15 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
     then use as they use the first hits.  Not together with `objects` (ValueError): a motion record moves
     real points, and a virtual point behind a mirror moves as the mirrored object does.
 
+    `variance`: "rendered" -- every pass takes the frame's standard error from the frame's own samples (the
+    error map; +inf at 1 spp, where nothing accumulates); "estimated" -- after the guides each frame runs
+    variance_estimate (with the motion table when `objects` is given; `variance_params`: None, an
+    api.VarianceParams or a dict of its fields) on a moment ping-pong of its own, and the reprojection or the
+    gather and the rectification, and the filter, take the estimated map wherever they took the rendered one.
+    Frames then also carry se_est (W*H) and moments (W*H*MOMENT_DOUBLES); se stays the map as rendered, and
+    samples = 1 is a normal input.  Without `temporal` and `denoise`, out_se is then se_est, not se: out_se is
+    always the standard error that goes with out.
+
     A generator: yields per frame a dict of float64 torch tensors on the scene's device -- image, se (the
     frame as rendered), feat, out, out_se (what the frame shows: accumulated and / or filtered; image and
     se themselves without either), and with `temporal` hist (W*H*HISTORY_DOUBLES) and accumulated /
@@ -453,6 +629,10 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
 
     if samples <= 0:
         raise ValueError("samples must be positive")
+    if variance not in ("rendered", "estimated"):
+        raise ValueError("variance must be \"rendered\" or \"estimated\", got %r" % (variance,))
+    est = variance == "estimated"
+    var_params = api.variance_params(variance_params_dict(variance_params)) if est else None
     if rectify is not None and rectify is not False and not temporal:
         raise ValueError("rectify needs temporal")
     rect = None if rectify is None or rectify is False or not temporal else \
@@ -470,11 +650,14 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
                      accumulated=torch.empty(npix * 4, **kw), accumulated_se=torch.empty(npix, **kw),
                      dn=torch.empty(npix * 4, **kw), dn_se=torch.empty(npix, **kw)) for _ in range(2)]
         work = torch.empty(api.denoise_work_bytes(w, h) // 8, **kw) if denoise else None
-        motion = torch.empty(api.MOTION_DOUBLES * 16, **kw) if objects is not None and temporal else None
+        motion = torch.empty(api.MOTION_DOUBLES * 16, **kw) if objects is not None and (temporal or est) else None
         gathered = torch.empty(npix * HISTORY_DOUBLES, **kw) if rect is not None else None
         if rect is not None:
             for buf in ring:
                 buf["rho"] = torch.empty(npix, **kw)
+        if est:
+            for buf in ring:
+                buf["moments"], buf["se_est"] = torch.empty(npix * MOMENT_DOUBLES, **kw), torch.empty(npix, **kw)
     prev, prev_cam, prev_objs, n_obj = None, None, None, 0
     frame_objects = iter(objects) if objects is not None else None
     for k, cam in enumerate(cameras):
@@ -494,25 +677,35 @@ def render_sequence(scene, cameras, samples, seed_stream, temporal=True, denoise
             scene.finalize(sums.data_ptr(), cur["image"].data_ptr(), samples, stream=sp)
             trace_guides(scene, cur["feat"].data_ptr(), guides, stream=sp)
             frame = dict(image=cur["image"], se=cur["se"], feat=cur["feat"], out=cur["image"], out_se=cur["se"])
+            se_ptr = cur["se"].data_ptr()  # the standard error the passes below take
+            if est:
+                moving = motion is not None and prev is not None
+                api.variance_estimate(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
+                                      prev["moments"].data_ptr() if prev else 0, prev["feat"].data_ptr() if prev else 0,
+                                      prev_cam, w, h, cur["moments"].data_ptr(), cur["se_est"].data_ptr(),
+                                      motion_ptr=motion.data_ptr() if moving else 0, n_obj=n_obj if moving else 0,
+                                      params=var_params, stream=sp)
+                se_ptr = cur["se_est"].data_ptr()
+                frame.update(se_est=cur["se_est"], moments=cur["moments"], out_se=cur["se_est"])
             if rect is not None:
                 moving = motion is not None and prev is not None
-                api.history_gather(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
+                api.history_gather(cur["image"].data_ptr(), se_ptr, cur["feat"].data_ptr(),
                                    prev["hist"].data_ptr() if prev else 0, prev["feat"].data_ptr() if prev else 0,
                                    prev_cam, w, h, gathered.data_ptr(), motion_ptr=motion.data_ptr() if moving else 0,
                                    n_obj=n_obj if moving else 0, params=reproject_params, stream=sp)
-                api.rectify(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(), gathered.data_ptr(),
+                api.rectify(cur["image"].data_ptr(), se_ptr, cur["feat"].data_ptr(), gathered.data_ptr(),
                             w, h, cur["hist"].data_ptr(), out_rgba_ptr=cur["accumulated"].data_ptr(),
                             out_se_ptr=cur["accumulated_se"].data_ptr(), params=rect, stream=sp)
                 cur["rho"].copy_(cur["hist"].view(npix, HISTORY_DOUBLES)[:, H_RHO])
                 frame.update(rho=cur["rho"])
             elif temporal and motion is not None and prev is not None:
-                api.reproject_motion(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
+                api.reproject_motion(cur["image"].data_ptr(), se_ptr, cur["feat"].data_ptr(),
                                      prev["hist"].data_ptr(), prev["feat"].data_ptr(), prev_cam, w, h,
                                      cur["hist"].data_ptr(), motion.data_ptr(), n_obj,
                                      out_rgba_ptr=cur["accumulated"].data_ptr(),
                                      out_se_ptr=cur["accumulated_se"].data_ptr(), params=reproject_params, stream=sp)
             elif temporal:
-                api.reproject(cur["image"].data_ptr(), cur["se"].data_ptr(), cur["feat"].data_ptr(),
+                api.reproject(cur["image"].data_ptr(), se_ptr, cur["feat"].data_ptr(),
                               prev["hist"].data_ptr() if prev else 0, prev["feat"].data_ptr() if prev else 0,
                               prev_cam, w, h, cur["hist"].data_ptr(), out_rgba_ptr=cur["accumulated"].data_ptr(),
                               out_se_ptr=cur["accumulated_se"].data_ptr(), params=reproject_params, stream=sp)
