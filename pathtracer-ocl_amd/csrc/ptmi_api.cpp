@@ -1,7 +1,9 @@
-// ptmi_api.cpp -- C ABI of libptmi.so (include/ptmi.h): record validation and
-// conversion to the HBM layout (ptmi_device.h), device residency, launch
-// orchestration.  Replaces the reference host driver internal/ocl/ocltracer.go
-// (Trace / computeBatch, ocltracer.go:98-376).
+// ptmi_api.cpp -- C ABI of libptmi.so (include/ptmi.h), the part that owns a ptmi_scene: record validation and
+// conversion to the HBM layout (ptmi_device.h), device residency, launch orchestration, the scene's feature
+// passes, the multi-GPU driver and the diagnostics.  Replaces the reference host driver
+// internal/ocl/ocltracer.go (Trace / computeBatch, ocltracer.go:98-376).  The image-space passes, which take
+// no scene, are in ptmi_image_api.cpp (their argument checks: ptmi_image_args.h); what both files share
+// (set_err, HIP_TRY, rd<>, convert_camera) is in ptmi_api_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +23,7 @@
 
 #include "../../include/ptmi.h"
 #include "../../include/ptmi_diag.h"
+#include "ptmi_api_internal.h"
 #include "ptmi_bvh.h"
 #include "ptmi_camcull.h"
 #include "ptmi_device.h"
@@ -157,35 +160,8 @@ struct ptmi_scene {
 // ptmi_diag_force_flags: kernel flags forced onto every scene created after the call
 // (-1: none).  Test hook for the generic instantiations.
 static std::atomic<int> g_force_flags{-1};
-// ptmi_diag_denoise_variant: the form of the a-trous pass (ptmi_image_kernels.hip launch_denoise).
-static std::atomic<int> g_denoise_variant{1};  // the LDS form: 2.20 against 3.01 ms (profiles/denoise/SUMMARY.md)
 
 namespace {
-
-void set_err(char* err, size_t n, const char* fmt, ...) {
-    if (!err || n == 0) return;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err, n, fmt, ap);
-    va_end(ap);
-}
-
-#define HIP_TRY(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            set_err(err, err_len, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-                    __LINE__);                                                                    \
-            return PTMI_ERR_HIP;                                                                  \
-        }                                                                                         \
-    } while (0)
-
-template <typename T>
-T rd(const uint8_t* p) {
-    T v;
-    std::memcpy(&v, p, sizeof(T));
-    return v;
-}
 
 int check_device(int idx, char* err, size_t err_len) {
     int n = 0;
@@ -222,27 +198,6 @@ bool is_diag3(const double* m) {  // rows 0-2 diagonal (row 3 unused)
     for (int i : z)
         if (m[i] != 0.0) return false;
     return true;
-}
-
-// The 256-byte CLCamera record -> DevCamera, origin included: the one conversion behind
-// ptmi_scene_create and ptmi_scene_set_camera, so both give the kernels the same bits.
-int convert_camera(const uint8_t* camera, DevCamera& cam, char* err, size_t err_len) {
-    cam.width = rd<int32_t>(camera + 0);
-    cam.height = rd<int32_t>(camera + 4);
-    cam.pixel_size = rd<double>(camera + 16);
-    cam.half_width = rd<double>(camera + 24);
-    cam.half_height = rd<double>(camera + 32);
-    cam.aperture = rd<double>(camera + 40);
-    cam.focal_length = rd<double>(camera + 48);
-    std::memcpy(cam.inv, camera + 56, 128);
-    for (int r = 0; r < 4; r++)  // mul (tracer.cl:369-376) of the point (0,0,0,1); no contraction (Makefile)
-        cam.origin[r] = ((cam.inv[4 * r] * 0.0 + cam.inv[4 * r + 1] * 0.0) + cam.inv[4 * r + 2] * 0.0) +
-                        cam.inv[4 * r + 3] * 1.0;
-    if (cam.width <= 0 || cam.height <= 0 || (int64_t)cam.width * cam.height > (int64_t)1 << 30) {
-        set_err(err, err_len, "bad camera size %dx%d", cam.width, cam.height);
-        return PTMI_ERR_ARG;
-    }
-    return PTMI_OK;
 }
 
 // One 1024-byte CLObject record -> DevObject (everything but its place in the scene: child_base, and for
@@ -1209,45 +1164,6 @@ int ptmi_scene_render_tiles(ptmi_scene* s, uint32_t samples, uint32_t sample_beg
                         err, err_len, tiles_dev, n_tiles);
 }
 
-int ptmi_select_tiles(const double* tile_err_dev, const uint32_t* in_tiles_dev, uint32_t n_in, double threshold,
-                      uint32_t* out_tiles_dev, uint32_t* count_dev, void* hip_stream, char* err, size_t err_len) {
-    if (!count_dev || (n_in > 0 && (!tile_err_dev || !out_tiles_dev)) || n_in > (1u << 31) ||
-        (n_in > 0 && out_tiles_dev == in_tiles_dev)) {
-        set_err(err, err_len, "bad select-tiles arguments (%u candidates)", n_in);
-        return PTMI_ERR_ARG;
-    }
-    HIP_TRY(launch_select_tiles(tile_err_dev, in_tiles_dev, n_in, threshold, out_tiles_dev, count_dev,
-                                (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-int ptmi_finalize_counts(const double* sums_dev, double* out_dev, uint32_t n_pixels, void* hip_stream, char* err,
-                         size_t err_len) {
-    if (!sums_dev || !out_dev) {
-        set_err(err, err_len, "bad finalize arguments");
-        return PTMI_ERR_ARG;
-    }
-    HIP_TRY(launch_finalize_counts(sums_dev, out_dev, n_pixels, (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-int ptmi_error_map(const double* sums_dev, const double* sq_dev, uint32_t width, uint32_t height, double* se_dev,
-                   double* tile_err_dev, double* stats_dev, void* hip_stream, char* err, size_t err_len) {
-    if (!sums_dev || !sq_dev || !stats_dev || width == 0 || height == 0) {
-        set_err(err, err_len, "bad error-map arguments");
-        return PTMI_ERR_ARG;
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    // The tiles' partial summaries between the two kernels: stream-ordered scratch.
-    const size_t tiles = (size_t)((width + kTile - 1) / kTile) * ((height + kTile - 1) / kTile);
-    double* tile_part = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&tile_part, tiles * 4 * sizeof(double), st));
-    const hipError_t e = launch_error_map(sums_dev, sq_dev, width, height, se_dev, tile_err_dev, tile_part, stats_dev, st);
-    HIP_TRY(hipFreeAsync(tile_part, st));
-    HIP_TRY(e);
-    return PTMI_OK;
-}
-
 int ptmi_scene_features(ptmi_scene* s, double* feat_dev, void* hip_stream, char* err, size_t err_len) {
     if (!s || !feat_dev || ((uintptr_t)feat_dev & 15u)) {
         set_err(err, err_len, "bad feature-pass arguments");
@@ -1271,51 +1187,6 @@ int ptmi_scene_features_chain(ptmi_scene* s, double* feat_dev, uint32_t max_chai
     }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(launch_features_chain(s->dev, feat_dev, max_chain, reflect_min, (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-size_t ptmi_denoise_work_bytes(uint32_t width, uint32_t height) {
-    return (size_t)width * (size_t)height * 2 * 4 * sizeof(double);  // two (r, g, b, var) states
-}
-
-int ptmi_denoise(const double* rgba_dev, const double* se_dev, const double* feat_dev, uint32_t width, uint32_t height,
-                 const ptmi_denoise_params* params, double* out_rgba_dev, double* out_se_dev, void* work_dev,
-                 size_t work_bytes, void* hip_stream, char* err, size_t err_len) {
-    ptmi_denoise_params p{5, PTMI_DENOISE_DEMODULATE, 4.0, 0.01, 7, 0};
-    if (params) p = *params;
-    if (!rgba_dev || !se_dev || !feat_dev || !out_rgba_dev || !work_dev || width == 0 || height == 0 ||
-        width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
-        set_err(err, err_len, "bad denoise arguments (%u x %u)", width, height);
-        return PTMI_ERR_ARG;
-    }
-    if (p.iterations < 1 || p.iterations > 8 || (p.flags & ~PTMI_DENOISE_DEMODULATE) || p.normal_power > 16 ||
-        !(std::isfinite(p.sigma_l) && p.sigma_l >= 0.0 && std::isfinite(p.sigma_d) && p.sigma_d >= 0.0)) {
-        set_err(err, err_len, "bad denoise parameters (iterations %u flags %u sigma_l %g sigma_d %g normal_power %u)",
-                p.iterations, p.flags, p.sigma_l, p.sigma_d, p.normal_power);
-        return PTMI_ERR_ARG;
-    }
-    if (work_bytes < ptmi_denoise_work_bytes(width, height)) {
-        set_err(err, err_len, "denoise workspace of %zu bytes, %zu needed", work_bytes,
-                ptmi_denoise_work_bytes(width, height));
-        return PTMI_ERR_ARG;
-    }
-    if (out_rgba_dev == rgba_dev || (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)out_rgba_dev |
-                                      (uintptr_t)work_dev) & 15u)) {
-        set_err(err, err_len, "denoise buffers aliased or not 16-byte aligned");
-        return PTMI_ERR_ARG;
-    }
-    const bool demod = (p.flags & PTMI_DENOISE_DEMODULATE) != 0;  // (outside HIP_TRY: its message quotes the call)
-    HIP_TRY(launch_denoise(rgba_dev, se_dev, feat_dev, width, height, p.iterations, demod, p.sigma_l, p.sigma_d, p.normal_power, out_rgba_dev,
-                           out_se_dev, (double*)work_dev, g_denoise_variant.load(), (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-int ptmi_accumulate(double* dst_dev, const double* src_dev, size_t n, void* hip_stream, char* err, size_t err_len) {
-    if (!dst_dev || !src_dev) {
-        set_err(err, err_len, "bad accumulate arguments");
-        return PTMI_ERR_ARG;
-    }
-    HIP_TRY(launch_accumulate(dst_dev, src_dev, n, (hipStream_t)hip_stream));
     return PTMI_OK;
 }
 
@@ -1471,293 +1342,6 @@ int ptmi_scene_set_objects(ptmi_scene* s, const void* objects, uint32_t n_obj, c
     return PTMI_OK;
 }
 
-int ptmi_motion_table(const void* prev_objects, const void* cur_objects, uint32_t n_obj, double* motion_dev,
-                      void* hip_stream, char* err, size_t err_len) {
-    if (!prev_objects || !cur_objects || !motion_dev || n_obj == 0 || n_obj > PTMI_MAX_OBJECTS ||
-        ((uintptr_t)motion_dev & 15u)) {
-        set_err(err, err_len, "bad motion table arguments (%u objects; NULL or misaligned pointer)", n_obj);
-        return PTMI_ERR_ARG;
-    }
-    double table[PTMI_MAX_OBJECTS * PTMI_MOTION_DOUBLES];
-    for (uint32_t k = 0; k < n_obj; k++)
-        motion_record((const uint8_t*)prev_objects + (size_t)PTMI_OBJECT_BYTES * k,
-                      (const uint8_t*)cur_objects + (size_t)PTMI_OBJECT_BYTES * k, table + PTMI_MOTION_DOUBLES * k);
-    // In stream order behind the work that still reads the buffer; `table` lives until the copy is done.
-    const size_t bytes = (size_t)n_obj * PTMI_MOTION_DOUBLES * sizeof(double);  // (outside HIP_TRY: its message quotes the call)
-    HIP_TRY(hipMemcpyAsync(motion_dev, table, bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-// The world-to-camera matrix of a camera record: the FP64 cofactor inverse of its `inverse`
-// (ptmi/temporal.py cofactor_inverse states the same operations).  false: singular or not finite.
-static bool cofactor_inverse(const double* m, double* out) {
-    auto det3 = [&](const int* r, const int* c) {
-        auto a = [&](int i, int j) { return m[4 * r[i] + c[j]]; };
-        return (a(0, 0) * (a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1)) - a(0, 1) * (a(1, 0) * a(2, 2) - a(1, 2) * a(2, 0))) +
-               a(0, 2) * (a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0));
-    };
-    double adj[16];
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {  // adj[i][j] = (-1)^(i+j) * minor of m without row j and column i
-            int r[3], c[3];
-            for (int k = 0, a = 0, b = 0; k < 4; k++) {
-                if (k != j) r[a++] = k;
-                if (k != i) c[b++] = k;
-            }
-            const double d = det3(r, c);
-            adj[4 * i + j] = ((i + j) & 1) ? -d : d;
-        }
-    const double det = ((m[0] * adj[0] + m[1] * adj[4]) + m[2] * adj[8]) + m[3] * adj[12];
-    if (!std::isfinite(det) || det == 0.0) return false;
-    for (int k = 0; k < 16; k++) {
-        out[k] = adj[k] / det;
-        if (!std::isfinite(out[k])) return false;
-    }
-    return true;
-}
-
-// The previous camera's part of a lookup's arguments (ptmi_reproject and its kin, ptmi_variance_estimate):
-// rows 0-2 of its world-to-camera matrix and its pixel mapping.  PTMI_ERR_ARG for a record that is singular,
-// not finite or of another size than the frame.
-static int previous_camera_args(const char* who, const void* prev_camera, uint32_t width, uint32_t height,
-                                ReprojectArgs& a, char* err, size_t err_len) {
-    DevCamera cam{};
-    if (const int rc = convert_camera((const uint8_t*)prev_camera, cam, err, err_len)) return rc;
-    double T[16];
-    if ((uint32_t)cam.width != width || (uint32_t)cam.height != height || !cofactor_inverse(cam.inv, T) ||
-        !(std::isfinite(cam.pixel_size) && cam.pixel_size > 0.0) || !std::isfinite(cam.half_width) ||
-        !std::isfinite(cam.half_height)) {
-        set_err(err, err_len, "%s: bad previous camera (%dx%d for a %ux%u frame, singular or non-finite)", who,
-                cam.width, cam.height, width, height);
-        return PTMI_ERR_ARG;
-    }
-    std::memcpy(a.T, T, sizeof(a.T));  // rows 0-2: the point's camera-space x, y, z
-    a.half_width = cam.half_width;
-    a.half_height = cam.half_height;
-    a.pixel_size = cam.pixel_size;
-    return PTMI_OK;
-}
-
-// ptmi_reproject (motion_dev == NULL, n_obj == 0), ptmi_reproject_motion and ptmi_history_gather (gather:
-// out_hist_dev is the gathered record, and there are no other outputs): one set of checks.
-static int reproject_checked(const double* rgba_dev, const double* se_dev, const double* feat_dev,
-                             const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
-                             uint32_t width, uint32_t height, const ptmi_reproject_params* params,
-                             double* out_hist_dev, double* out_rgba_dev, double* out_se_dev, const double* motion_dev,
-                             uint32_t n_obj, bool gather, void* hip_stream, char* err, size_t err_len) {
-    ptmi_reproject_params p{32, 0, 0.9, 0.02, 0.05};
-    if (params) p = *params;
-    if (!rgba_dev || !se_dev || !feat_dev || !out_hist_dev || (prev_hist_dev && (!prev_feat_dev || !prev_camera)) ||
-        width == 0 || height == 0 || width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
-        set_err(err, err_len, "bad reproject arguments (%u x %u)", width, height);
-        return PTMI_ERR_ARG;
-    }
-    auto good = [](double v) { return std::isfinite(v) && v >= 0.0; };
-    if (p.max_history < 1 || p.max_history > 65536 || p.flags != 0 || !good(p.normal_cos) || !good(p.plane_dist) ||
-        !good(p.min_weight)) {
-        set_err(err, err_len, "bad reproject parameters (max_history %u flags %u normal_cos %g plane_dist %g min_weight %g)",
-                p.max_history, p.flags, p.normal_cos, p.plane_dist, p.min_weight);
-        return PTMI_ERR_ARG;
-    }
-    // No output may overlap an input or another output (the kernel's pointers are __restrict__).
-    const size_t npix = (size_t)width * height;
-    struct Range {
-        const double* p;
-        size_t doubles;
-    };
-    const Range ins[6] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
-                          {prev_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {prev_feat_dev, npix * PTMI_FEATURE_DOUBLES},
-                          {motion_dev, (size_t)n_obj * PTMI_MOTION_DOUBLES}};
-    const Range outs[3] = {{out_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {out_rgba_dev, npix * 4}, {out_se_dev, npix}};
-    auto overlap = [](const Range& a, const Range& b) {
-        if (!a.p || !b.p) return false;
-        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-        return a0 < b0 + b.doubles * sizeof(double) && b0 < a0 + a.doubles * sizeof(double);
-    };
-    bool aliased = false;
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 6; i++) aliased = aliased || overlap(outs[o], ins[i]);
-        for (int q = o + 1; q < 3; q++) aliased = aliased || overlap(outs[o], outs[q]);
-    }
-    if (aliased ||
-        (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)prev_hist_dev | (uintptr_t)prev_feat_dev |
-          (uintptr_t)out_hist_dev | (uintptr_t)out_rgba_dev | (uintptr_t)motion_dev) & 15u)) {
-        set_err(err, err_len, "reproject buffers overlap or are not 16-byte aligned");
-        return PTMI_ERR_ARG;
-    }
-    ReprojectArgs a{};
-    a.W = (int32_t)width;
-    a.H = (int32_t)height;
-    a.max_history = (double)p.max_history;
-    a.normal_cos = p.normal_cos;
-    a.plane_dist = p.plane_dist;
-    a.min_weight = p.min_weight;
-    if (prev_camera)
-        if (const int rc = previous_camera_args("reproject", prev_camera, width, height, a, err, err_len)) return rc;
-    if (gather)
-        HIP_TRY(launch_history_gather(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev,
-                                      motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
-    else
-        HIP_TRY(launch_reproject(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, a, out_hist_dev,
-                                 out_rgba_dev, out_se_dev, motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-int ptmi_reproject(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* prev_hist_dev,
-                   const double* prev_feat_dev, const void* prev_camera, uint32_t width, uint32_t height,
-                   const ptmi_reproject_params* params, double* out_hist_dev, double* out_rgba_dev, double* out_se_dev,
-                   void* hip_stream, char* err, size_t err_len) {
-    return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
-                             out_hist_dev, out_rgba_dev, out_se_dev, nullptr, 0, false, hip_stream, err, err_len);
-}
-
-int ptmi_reproject_motion(const double* rgba_dev, const double* se_dev, const double* feat_dev,
-                          const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
-                          uint32_t width, uint32_t height, const ptmi_reproject_params* params, double* out_hist_dev,
-                          double* out_rgba_dev, double* out_se_dev, const double* motion_dev, uint32_t n_obj,
-                          void* hip_stream, char* err, size_t err_len) {
-    if (!motion_dev || n_obj == 0 || n_obj > PTMI_MAX_OBJECTS) {
-        set_err(err, err_len, "bad reproject arguments (motion table NULL or of %u objects)", n_obj);
-        return PTMI_ERR_ARG;
-    }
-    return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
-                             out_hist_dev, out_rgba_dev, out_se_dev, motion_dev, n_obj, false, hip_stream, err, err_len);
-}
-
-int ptmi_history_gather(const double* rgba_dev, const double* se_dev, const double* feat_dev,
-                        const double* prev_hist_dev, const double* prev_feat_dev, const void* prev_camera,
-                        uint32_t width, uint32_t height, const ptmi_reproject_params* params, double* gathered_dev,
-                        const double* motion_dev, uint32_t n_obj, void* hip_stream, char* err, size_t err_len) {
-    if ((motion_dev == nullptr) != (n_obj == 0) || n_obj > PTMI_MAX_OBJECTS) {
-        set_err(err, err_len, "bad history_gather arguments (motion table %s, %u objects)", motion_dev ? "given" : "NULL",
-                n_obj);
-        return PTMI_ERR_ARG;
-    }
-    return reproject_checked(rgba_dev, se_dev, feat_dev, prev_hist_dev, prev_feat_dev, prev_camera, width, height, params,
-                             gathered_dev, nullptr, nullptr, motion_dev, n_obj, true, hip_stream, err, err_len);
-}
-
-int ptmi_rectify(const double* rgba_dev, const double* se_dev, const double* feat_dev, const double* gathered_dev,
-                 uint32_t width, uint32_t height, const ptmi_rectify_params* params, double* out_hist_dev,
-                 double* out_rgba_dev, double* out_se_dev, void* hip_stream, char* err, size_t err_len) {
-    ptmi_rectify_params p{3, 9, 3.0, 32, 0};
-    if (params) p = *params;
-    if (!rgba_dev || !se_dev || !feat_dev || !gathered_dev || !out_hist_dev || width == 0 || height == 0 ||
-        width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
-        set_err(err, err_len, "bad rectify arguments (%u x %u)", width, height);
-        return PTMI_ERR_ARG;
-    }
-    if (p.radius < 1 || p.radius > 4 || !(std::isfinite(p.gamma) && p.gamma >= 0.0) || p.max_history < 1 ||
-        p.max_history > 65536 || p.flags != 0) {
-        set_err(err, err_len, "bad rectify parameters (radius %u min_count %u gamma %g max_history %u flags %u)", p.radius,
-                p.min_count, p.gamma, p.max_history, p.flags);
-        return PTMI_ERR_ARG;
-    }
-    // No output may overlap an input or another output (the kernel's pointers are __restrict__).
-    const size_t npix = (size_t)width * height;
-    struct Range {
-        const double* p;
-        size_t doubles;
-    };
-    const Range ins[4] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
-                          {gathered_dev, npix * PTMI_HISTORY_DOUBLES}};
-    const Range outs[3] = {{out_hist_dev, npix * PTMI_HISTORY_DOUBLES}, {out_rgba_dev, npix * 4}, {out_se_dev, npix}};
-    auto overlap = [](const Range& a, const Range& b) {
-        if (!a.p || !b.p) return false;
-        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-        return a0 < b0 + b.doubles * sizeof(double) && b0 < a0 + a.doubles * sizeof(double);
-    };
-    bool aliased = false;
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 4; i++) aliased = aliased || overlap(outs[o], ins[i]);
-        for (int q = o + 1; q < 3; q++) aliased = aliased || overlap(outs[o], outs[q]);
-    }
-    if (aliased || (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)gathered_dev | (uintptr_t)out_hist_dev |
-                     (uintptr_t)out_rgba_dev) & 15u)) {
-        set_err(err, err_len, "rectify buffers overlap or are not 16-byte aligned");
-        return PTMI_ERR_ARG;
-    }
-    RectifyArgs a{};
-    a.W = (int32_t)width;
-    a.H = (int32_t)height;
-    a.min_count = p.min_count;
-    a.gamma2 = p.gamma * p.gamma;
-    a.max_history = (double)p.max_history;
-    HIP_TRY(launch_rectify(rgba_dev, se_dev, feat_dev, gathered_dev, a, p.radius, out_hist_dev, out_rgba_dev, out_se_dev,
-                           (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-int ptmi_variance_estimate(const double* rgba_dev, const double* se_dev, const double* feat_dev,
-                           const double* prev_mom_dev, const double* prev_feat_dev, const void* prev_camera,
-                           uint32_t width, uint32_t height, const ptmi_variance_params* params, double* out_mom_dev,
-                           double* out_se_dev, const double* motion_dev, uint32_t n_obj, void* hip_stream, char* err,
-                           size_t err_len) {
-    ptmi_variance_params p{32, 4, 3, 9, 0, 0.9, 0.02, 0.05, 0.9};
-    if (params) p = *params;
-    if (!rgba_dev || !feat_dev || !out_mom_dev || !out_se_dev || (prev_mom_dev && (!prev_feat_dev || !prev_camera)) ||
-        width == 0 || height == 0 || width > 65536 || height > 65536 || (uint64_t)width * height > (1ull << 31)) {
-        set_err(err, err_len, "bad variance_estimate arguments (%u x %u)", width, height);
-        return PTMI_ERR_ARG;
-    }
-    if ((motion_dev == nullptr) != (n_obj == 0) || n_obj > PTMI_MAX_OBJECTS) {
-        set_err(err, err_len, "bad variance_estimate arguments (motion table %s, %u objects)",
-                motion_dev ? "given" : "NULL", n_obj);
-        return PTMI_ERR_ARG;
-    }
-    auto good = [](double v) { return std::isfinite(v) && v >= 0.0; };
-    if (p.max_history < 1 || p.max_history > 65536 || p.min_temporal < 2 || p.min_temporal > 65536 || p.radius < 1 ||
-        p.radius > 4 || p.min_count < 2 || p.flags != 0 || !good(p.normal_cos) || !good(p.plane_dist) ||
-        !good(p.min_weight) || !good(p.window_normal_cos)) {
-        set_err(err, err_len,
-                "bad variance parameters (max_history %u min_temporal %u radius %u min_count %u flags %u normal_cos %g "
-                "plane_dist %g min_weight %g window_normal_cos %g)",
-                p.max_history, p.min_temporal, p.radius, p.min_count, p.flags, p.normal_cos, p.plane_dist, p.min_weight,
-                p.window_normal_cos);
-        return PTMI_ERR_ARG;
-    }
-    // No output may overlap an input or another output (the kernel's pointers are __restrict__).
-    const size_t npix = (size_t)width * height;
-    struct Range {
-        const double* p;
-        size_t doubles;
-    };
-    const Range ins[6] = {{rgba_dev, npix * 4}, {se_dev, npix}, {feat_dev, npix * PTMI_FEATURE_DOUBLES},
-                          {prev_mom_dev, npix * PTMI_MOMENT_DOUBLES}, {prev_feat_dev, npix * PTMI_FEATURE_DOUBLES},
-                          {motion_dev, (size_t)n_obj * PTMI_MOTION_DOUBLES}};
-    const Range outs[2] = {{out_mom_dev, npix * PTMI_MOMENT_DOUBLES}, {out_se_dev, npix}};
-    auto overlap = [](const Range& a, const Range& b) {
-        if (!a.p || !b.p) return false;
-        const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-        return a0 < b0 + b.doubles * sizeof(double) && b0 < a0 + a.doubles * sizeof(double);
-    };
-    bool aliased = overlap(outs[0], outs[1]);
-    for (int o = 0; o < 2; o++)
-        for (int i = 0; i < 6; i++) aliased = aliased || overlap(outs[o], ins[i]);
-    if (aliased || (((uintptr_t)rgba_dev | (uintptr_t)feat_dev | (uintptr_t)prev_mom_dev | (uintptr_t)prev_feat_dev |
-                     (uintptr_t)out_mom_dev | (uintptr_t)motion_dev) & 15u)) {
-        set_err(err, err_len, "variance_estimate buffers overlap or are not 16-byte aligned");
-        return PTMI_ERR_ARG;
-    }
-    VarianceArgs a{};
-    a.r.W = (int32_t)width;
-    a.r.H = (int32_t)height;
-    a.r.max_history = (double)p.max_history;
-    a.r.normal_cos = p.normal_cos;
-    a.r.plane_dist = p.plane_dist;
-    a.r.min_weight = p.min_weight;
-    a.min_temporal = (double)p.min_temporal;
-    a.window_normal_cos = p.window_normal_cos;
-    a.min_count = p.min_count;
-    if (prev_camera)
-        if (const int rc = previous_camera_args("variance_estimate", prev_camera, width, height, a.r, err, err_len))
-            return rc;
-    HIP_TRY(launch_variance(rgba_dev, se_dev, feat_dev, prev_mom_dev, prev_feat_dev, a, p.radius, out_mom_dev, out_se_dev,
-                            motion_dev, (int32_t)n_obj, (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
 int ptmi_scene_set_timing(ptmi_scene* s, int enable) {
     if (!s) return PTMI_ERR_ARG;
     s->timing = enable != 0;
@@ -1782,26 +1366,6 @@ int ptmi_scene_kernel_time(ptmi_scene* s, double* total_ms, uint32_t* launches, 
     if (total_ms) *total_ms = tot;
     if (launches) *launches = (uint32_t)s->events.size();
     s->events.clear();
-    return PTMI_OK;
-}
-
-int ptmi_finalize(const double* sums_dev, double* out_dev, uint32_t n_pixels, uint32_t samples, void* hip_stream,
-                  char* err, size_t err_len) {
-    if (!sums_dev || !out_dev || samples == 0) {
-        set_err(err, err_len, "bad finalize arguments");
-        return PTMI_ERR_ARG;
-    }
-    HIP_TRY(launch_finalize(sums_dev, out_dev, n_pixels, samples, (hipStream_t)hip_stream));
-    return PTMI_OK;
-}
-
-int ptmi_fill_seeds(double* seeds_dev, uint32_t n, uint64_t seed_stream, void* hip_stream, char* err,
-                    size_t err_len) {
-    if (!seeds_dev) {
-        set_err(err, err_len, "seeds_dev == NULL");
-        return PTMI_ERR_ARG;
-    }
-    HIP_TRY(launch_seeds(seeds_dev, n, seed_stream, (hipStream_t)hip_stream));
     return PTMI_OK;
 }
 
@@ -2023,18 +1587,6 @@ extern "C" int ptmi_trace_multi_timed(const void* objects, uint32_t n_obj, const
         timing->peer_direct = (int32_t)std::count(peer.begin(), peer.end(), 1);
         timing->peer_staged = (int32_t)std::count(peer.begin(), peer.end(), 0);
     }
-    return PTMI_OK;
-}
-
-// The device-side combine of ptmi_trace_multi, for callers that gather their own partial
-// frames (one per GPU) into one device buffer: slots summed in slot order, x 1/S, alpha 1.
-extern "C" int ptmi_combine_frames(const double* parts_dev, uint32_t n_parts, uint32_t n_pixels, double* out_dev,
-                                   uint32_t samples, void* hip_stream, char* err, size_t err_len) {
-    if (!parts_dev || !out_dev || n_parts == 0 || samples == 0) {
-        set_err(err, err_len, "bad combine arguments");
-        return PTMI_ERR_ARG;
-    }
-    HIP_TRY(launch_combine(parts_dev, n_parts, n_pixels, out_dev, samples, (hipStream_t)hip_stream));
     return PTMI_OK;
 }
 
@@ -2274,11 +1826,6 @@ extern "C" int ptmi_diag_force_flags(int flags) {
     if (flags > F_GENERIC) return PTMI_ERR_ARG;
     g_force_flags.store(flags < 0 ? -1 : flags);
     return PTMI_OK;
-}
-
-extern "C" int ptmi_diag_denoise_variant(int variant) {
-    if (variant < 0 || variant > 1) return -1;
-    return g_denoise_variant.exchange(variant);
 }
 
 extern "C" int ptmi_diag_hemi_mismatch(const ptmi_scene* s) { return s ? s->hemi_mismatch : -1; }

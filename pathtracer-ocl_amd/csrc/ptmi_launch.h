@@ -1,5 +1,5 @@
 // ptmi_launch.h -- the host-side launch wrappers that the two kernel files define and ptmi_api.cpp calls,
-// declared once for all three, so the compiler checks each definition against its declaration.  The study
+// declared once for the API files, so the compiler checks each definition against its declaration.  The study
 // ones exist in the study build only (PTMI_STUDY; a file that never names it reads 0 here and does not
 // define them).
 #pragma once

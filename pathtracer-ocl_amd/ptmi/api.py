@@ -241,6 +241,22 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None and len(a) else None
 
 
+def _vp(address):
+    """A device address (or a stream) as the library takes it; 0 and None are NULL."""
+    return ctypes.c_void_p(address or None)
+
+
+def _params(cls, params):
+    """A parameter record of class `cls` from None (the library's defaults), a `cls` or a dict of some fields."""
+    if params is None or isinstance(params, cls):
+        return params
+    return cls(**dict(params))
+
+
+def _ref(p):
+    return ctypes.byref(p) if p is not None else None
+
+
 def _records(objects, triangles, groups, camera):
     objects = np.ascontiguousarray(objects)
     triangles = np.ascontiguousarray(triangles) if triangles is not None else np.zeros(0, layout.TRIANGLE_DTYPE)
@@ -322,8 +338,8 @@ def combine_frames(parts_ptr, n_parts, n_pixels, out_ptr, samples, stream=0):
     """ptmi_combine_frames: n_parts partial frames (device memory, back to back) summed
     in part order and normalised into out_ptr (may equal parts_ptr)."""
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_combine_frames(ctypes.c_void_p(parts_ptr), int(n_parts), int(n_pixels),
-                                              ctypes.c_void_p(out_ptr), int(samples), ctypes.c_void_p(stream),
+    _check(load_library().ptmi_combine_frames(_vp(parts_ptr), int(n_parts), int(n_pixels),
+                                              _vp(out_ptr), int(samples), _vp(stream),
                                               err, len(err)), err)
 
 
@@ -425,8 +441,8 @@ class Scene:
                chunks=0, stream=0):
         err = ctypes.create_string_buffer(1024)
         rc = self._lib.ptmi_scene_render(self._h, samples, sample_begin, sample_end, tile_stride, tile_offset,
-                                         ctypes.c_void_p(seeds_ptr), ctypes.c_void_p(sums_ptr), chunks,
-                                         ctypes.c_void_p(stream), err, len(err))
+                                         _vp(seeds_ptr), _vp(sums_ptr), chunks,
+                                         _vp(stream), err, len(err))
         _check(rc, err)
 
     def render_moments(self, samples, sample_begin, sample_end, seeds_ptr, sums_ptr, sq_ptr, tile_stride=1,
@@ -435,8 +451,8 @@ class Scene:
         the range's paths of (r*r + g*g) + b*b, 0 elsewhere.  The sums are render()'s bit for bit."""
         err = ctypes.create_string_buffer(1024)
         rc = self._lib.ptmi_scene_render_moments(self._h, samples, sample_begin, sample_end, tile_stride, tile_offset,
-                                                 ctypes.c_void_p(seeds_ptr), ctypes.c_void_p(sums_ptr),
-                                                 ctypes.c_void_p(sq_ptr), chunks, ctypes.c_void_p(stream), err,
+                                                 _vp(seeds_ptr), _vp(sums_ptr),
+                                                 _vp(sq_ptr), chunks, _vp(stream), err,
                                                  len(err))
         _check(rc, err)
 
@@ -447,9 +463,9 @@ class Scene:
         is set to 0.  An index past the frame's tiles is skipped."""
         err = ctypes.create_string_buffer(1024)
         rc = self._lib.ptmi_scene_render_tiles(self._h, samples, sample_begin, sample_end,
-                                               ctypes.c_void_p(tiles_ptr or None), int(n_tiles),
-                                               ctypes.c_void_p(seeds_ptr), ctypes.c_void_p(sums_ptr),
-                                               ctypes.c_void_p(sq_ptr or None), chunks, ctypes.c_void_p(stream), err,
+                                               _vp(tiles_ptr), int(n_tiles),
+                                               _vp(seeds_ptr), _vp(sums_ptr),
+                                               _vp(sq_ptr), chunks, _vp(stream), err,
                                                len(err))
         _check(rc, err)
 
@@ -459,8 +475,8 @@ class Scene:
 
     def finalize(self, sums_ptr, out_ptr, samples, stream=0):
         err = ctypes.create_string_buffer(1024)
-        rc = self._lib.ptmi_finalize(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(out_ptr),
-                                     self.width * self.height, samples, ctypes.c_void_p(stream), err, len(err))
+        rc = self._lib.ptmi_finalize(_vp(sums_ptr), _vp(out_ptr),
+                                     self.width * self.height, samples, _vp(stream), err, len(err))
         _check(rc, err)
 
     def features(self, feat_ptr, stream=0, chain=False, max_chain=8, reflect_min=0.5):
@@ -471,11 +487,11 @@ class Scene:
         recorded at its virtual position, with the chain's length in slot [11]."""
         err = ctypes.create_string_buffer(256)
         if chain:
-            _check(self._lib.ptmi_scene_features_chain(self._h, ctypes.c_void_p(feat_ptr or None), int(max_chain),
-                                                       float(reflect_min), ctypes.c_void_p(stream), err, len(err)),
+            _check(self._lib.ptmi_scene_features_chain(self._h, _vp(feat_ptr), int(max_chain),
+                                                       float(reflect_min), _vp(stream), err, len(err)),
                    err)
             return
-        _check(self._lib.ptmi_scene_features(self._h, ctypes.c_void_p(feat_ptr or None), ctypes.c_void_p(stream), err,
+        _check(self._lib.ptmi_scene_features(self._h, _vp(feat_ptr), _vp(stream), err,
                                              len(err)), err)
 
     def set_camera(self, camera_record):
@@ -580,10 +596,8 @@ class Scene:
 
 
 def fill_seeds(seeds_ptr, n, seed_stream, stream=0):
-    lib = load_library()
     err = ctypes.create_string_buffer(256)
-    _check(lib.ptmi_fill_seeds(ctypes.c_void_p(seeds_ptr), n, seed_stream, ctypes.c_void_p(stream), err, len(err)),
-           err)
+    _check(load_library().ptmi_fill_seeds(_vp(seeds_ptr), n, seed_stream, _vp(stream), err, len(err)), err)
 
 
 def error_map(sums_ptr, sq_ptr, width, height, stats_ptr, se_ptr=0, tile_err_ptr=0, stream=0):
@@ -593,17 +607,15 @@ def error_map(sums_ptr, sq_ptr, width, height, stats_ptr, se_ptr=0, tile_err_ptr
     finite one, mean of the pixel means, pixel count) over the pixels with n >= 2.  The formula is
     ptmi/error.py error_map_reference."""
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_error_map(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(sq_ptr), int(width), int(height),
-                                         ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(tile_err_ptr or None),
-                                         ctypes.c_void_p(stats_ptr), ctypes.c_void_p(stream), err, len(err)), err)
+    _check(load_library().ptmi_error_map(_vp(sums_ptr), _vp(sq_ptr), int(width), int(height), _vp(se_ptr),
+                                         _vp(tile_err_ptr), _vp(stats_ptr), _vp(stream), err, len(err)), err)
 
 
 def accumulate(dst_ptr, src_ptr, n, stream=0):
     """ptmi_accumulate: dst[k] += src[k] over n doubles of device memory (batches of sums, whose
     fourth slots -- the sample counts -- add too, and of second moments)."""
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_accumulate(ctypes.c_void_p(dst_ptr), ctypes.c_void_p(src_ptr), int(n),
-                                          ctypes.c_void_p(stream), err, len(err)), err)
+    _check(load_library().ptmi_accumulate(_vp(dst_ptr), _vp(src_ptr), int(n), _vp(stream), err, len(err)), err)
 
 
 def select_tiles(tile_err_ptr, in_tiles_ptr, n_in, threshold, out_tiles_ptr, count_ptr, stream=0):
@@ -612,17 +624,16 @@ def select_tiles(tile_err_ptr, in_tiles_ptr, n_in, threshold, out_tiles_ptr, cou
     their number to count_ptr[0] (uint32).  NaN and ties are dropped, +inf is kept; the two lists must
     not alias.  The rule is ptmi/error.py select_tiles_reference."""
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_select_tiles(ctypes.c_void_p(tile_err_ptr or None), ctypes.c_void_p(in_tiles_ptr or None),
-                                            int(n_in), float(threshold), ctypes.c_void_p(out_tiles_ptr or None),
-                                            ctypes.c_void_p(count_ptr), ctypes.c_void_p(stream), err, len(err)), err)
+    _check(load_library().ptmi_select_tiles(_vp(tile_err_ptr), _vp(in_tiles_ptr), int(n_in), float(threshold),
+                                            _vp(out_tiles_ptr), _vp(count_ptr), _vp(stream), err, len(err)), err)
 
 
 def finalize_counts(sums_ptr, out_ptr, n_pixels, stream=0):
     """ptmi_finalize_counts: RGB = sum_c * (1.0 / n) with the pixel's own n = sums[4i+3] (0 where
     n == 0), A = 1.0.  The rule is ptmi/error.py finalize_counts_reference."""
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_finalize_counts(ctypes.c_void_p(sums_ptr), ctypes.c_void_p(out_ptr), int(n_pixels),
-                                               ctypes.c_void_p(stream), err, len(err)), err)
+    _check(load_library().ptmi_finalize_counts(_vp(sums_ptr), _vp(out_ptr), int(n_pixels), _vp(stream), err, len(err)),
+           err)
 
 
 def denoise_work_bytes(width, height):
@@ -632,9 +643,7 @@ def denoise_work_bytes(width, height):
 
 def denoise_params(params=None):
     """A DenoiseParams from None (the defaults), a DenoiseParams or a dict of some of its fields."""
-    if params is None or isinstance(params, DenoiseParams):
-        return params
-    return DenoiseParams(**dict(params))
+    return _params(DenoiseParams, params)
 
 
 def denoise(rgba_ptr, se_ptr, feat_ptr, w, h, out_ptr, out_se_ptr=0, params=None, stream=0, work=None):
@@ -649,18 +658,24 @@ def denoise(rgba_ptr, se_ptr, feat_ptr, w, h, out_ptr, out_se_ptr=0, params=None
         import torch
         work = torch.empty(denoise_work_bytes(w, h) // 8, dtype=torch.float64, device="cuda")
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_denoise(ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None),
-                                       ctypes.c_void_p(feat_ptr or None), int(w), int(h),
-                                       ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_ptr or None),
-                                       ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(work.data_ptr()),
-                                       work.numel() * work.element_size(), ctypes.c_void_p(stream), err, len(err)), err)
+    _check(load_library().ptmi_denoise(_vp(rgba_ptr), _vp(se_ptr), _vp(feat_ptr), int(w), int(h), _ref(p), _vp(out_ptr),
+                                       _vp(out_se_ptr), _vp(work.data_ptr()), work.numel() * work.element_size(),
+                                       _vp(stream), err, len(err)), err)
 
 
 def reproject_params(params=None):
     """A ReprojectParams from None (the defaults), a ReprojectParams or a dict of some of its fields."""
-    if params is None or isinstance(params, ReprojectParams):
-        return params
-    return ReprojectParams(**dict(params))
+    return _params(ReprojectParams, params)
+
+
+def _camera_record(prev_camera):
+    if prev_camera is None:
+        return None
+    cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
+    if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
+        raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
+                                                                           cam.dtype.itemsize))
+    return cam
 
 
 def reproject(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_camera, w, h, out_hist_ptr,
@@ -673,20 +688,11 @@ def reproject(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_cam
     params: None, a ReprojectParams or a dict of its fields.  The operation order is ptmi/temporal.py
     reproject_reference."""
     p = reproject_params(params)
-    cam = None
-    if prev_camera is not None:
-        cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
-        if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
-            raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
-                                                                               cam.dtype.itemsize))
+    cam = _camera_record(prev_camera)
     err = ctypes.create_string_buffer(512)
-    _check(load_library().ptmi_reproject(ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None),
-                                         ctypes.c_void_p(feat_ptr or None), ctypes.c_void_p(prev_hist_ptr or None),
-                                         ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
-                                         ctypes.byref(p) if p is not None else None,
-                                         ctypes.c_void_p(out_hist_ptr or None), ctypes.c_void_p(out_rgba_ptr or None),
-                                         ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(stream), err, len(err)),
-           err)
+    _check(load_library().ptmi_reproject(
+        _vp(rgba_ptr), _vp(se_ptr), _vp(feat_ptr), _vp(prev_hist_ptr), _vp(prev_feat_ptr), _ptr(cam), int(w), int(h),
+        _ref(p), _vp(out_hist_ptr), _vp(out_rgba_ptr), _vp(out_se_ptr), _vp(stream), err, len(err)), err)
 
 
 def _object_records(objects, name):
@@ -708,8 +714,8 @@ def motion_table(prev_objects, cur_objects, motion_ptr, n_obj=None, stream=0):
             raise ValueError("motion_table: two object lists of one length")
         n_obj = len(cur)
     err = ctypes.create_string_buffer(256)
-    _check(load_library().ptmi_motion_table(_ptr(prev), _ptr(cur), int(n_obj), ctypes.c_void_p(motion_ptr or None),
-                                            ctypes.c_void_p(stream), err, len(err)), err)
+    _check(load_library().ptmi_motion_table(_ptr(prev), _ptr(cur), int(n_obj), _vp(motion_ptr),
+                                            _vp(stream), err, len(err)), err)
 
 
 def reproject_motion(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_camera, w, h, out_hist_ptr,
@@ -720,29 +726,12 @@ def reproject_motion(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, p
     outputs are reproject()'s bit for bit.  The operation order is ptmi/temporal.py reproject_reference
     with `motion`."""
     p = reproject_params(params)
-    cam = None
-    if prev_camera is not None:
-        cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
-        if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
-            raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
-                                                                               cam.dtype.itemsize))
+    cam = _camera_record(prev_camera)
     err = ctypes.create_string_buffer(512)
     _check(load_library().ptmi_reproject_motion(
-        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
-        ctypes.c_void_p(prev_hist_ptr or None), ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
-        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_hist_ptr or None),
-        ctypes.c_void_p(out_rgba_ptr or None), ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(motion_ptr or None),
-        int(n_obj), ctypes.c_void_p(stream), err, len(err)), err)
-
-
-def _camera_record(prev_camera):
-    if prev_camera is None:
-        return None
-    cam = np.ascontiguousarray(np.asarray(prev_camera).reshape(1))
-    if cam.dtype.itemsize != layout.CAMERA_DTYPE.itemsize:
-        raise TypeError("prev_camera: expected %d-byte records, got %d" % (layout.CAMERA_DTYPE.itemsize,
-                                                                           cam.dtype.itemsize))
-    return cam
+        _vp(rgba_ptr), _vp(se_ptr), _vp(feat_ptr), _vp(prev_hist_ptr), _vp(prev_feat_ptr), _ptr(cam), int(w), int(h),
+        _ref(p), _vp(out_hist_ptr), _vp(out_rgba_ptr), _vp(out_se_ptr), _vp(motion_ptr), int(n_obj), _vp(stream), err,
+        len(err)), err)
 
 
 def history_gather(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, prev_camera, w, h, gathered_ptr,
@@ -755,17 +744,13 @@ def history_gather(rgba_ptr, se_ptr, feat_ptr, prev_hist_ptr, prev_feat_ptr, pre
     cam = _camera_record(prev_camera)
     err = ctypes.create_string_buffer(512)
     _check(load_library().ptmi_history_gather(
-        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
-        ctypes.c_void_p(prev_hist_ptr or None), ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
-        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(gathered_ptr or None),
-        ctypes.c_void_p(motion_ptr or None), int(n_obj), ctypes.c_void_p(stream), err, len(err)), err)
+        _vp(rgba_ptr), _vp(se_ptr), _vp(feat_ptr), _vp(prev_hist_ptr), _vp(prev_feat_ptr), _ptr(cam), int(w), int(h),
+        _ref(p), _vp(gathered_ptr), _vp(motion_ptr), int(n_obj), _vp(stream), err, len(err)), err)
 
 
 def rectify_params(params=None):
     """A RectifyParams from None (the defaults), a RectifyParams or a dict of some of its fields."""
-    if params is None or isinstance(params, RectifyParams):
-        return params
-    return RectifyParams(**dict(params))
+    return _params(RectifyParams, params)
 
 
 def rectify(rgba_ptr, se_ptr, feat_ptr, gathered_ptr, w, h, out_hist_ptr, out_rgba_ptr=0, out_se_ptr=0, params=None,
@@ -778,17 +763,13 @@ def rectify(rgba_ptr, se_ptr, feat_ptr, gathered_ptr, w, h, out_hist_ptr, out_rg
     p = rectify_params(params)
     err = ctypes.create_string_buffer(512)
     _check(load_library().ptmi_rectify(
-        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
-        ctypes.c_void_p(gathered_ptr or None), int(w), int(h), ctypes.byref(p) if p is not None else None,
-        ctypes.c_void_p(out_hist_ptr or None), ctypes.c_void_p(out_rgba_ptr or None),
-        ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(stream), err, len(err)), err)
+        _vp(rgba_ptr), _vp(se_ptr), _vp(feat_ptr), _vp(gathered_ptr), int(w), int(h), _ref(p), _vp(out_hist_ptr),
+        _vp(out_rgba_ptr), _vp(out_se_ptr), _vp(stream), err, len(err)), err)
 
 
 def variance_params(params=None):
     """A VarianceParams from None (the defaults), a VarianceParams or a dict of some of its fields."""
-    if params is None or isinstance(params, VarianceParams):
-        return params
-    return VarianceParams(**dict(params))
+    return _params(VarianceParams, params)
 
 
 def variance_estimate(rgba_ptr, se_ptr, feat_ptr, prev_mom_ptr, prev_feat_ptr, prev_camera, w, h, out_mom_ptr,
@@ -805,8 +786,5 @@ def variance_estimate(rgba_ptr, se_ptr, feat_ptr, prev_mom_ptr, prev_feat_ptr, p
     cam = _camera_record(prev_camera)
     err = ctypes.create_string_buffer(512)
     _check(load_library().ptmi_variance_estimate(
-        ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(se_ptr or None), ctypes.c_void_p(feat_ptr or None),
-        ctypes.c_void_p(prev_mom_ptr or None), ctypes.c_void_p(prev_feat_ptr or None), _ptr(cam), int(w), int(h),
-        ctypes.byref(p) if p is not None else None, ctypes.c_void_p(out_mom_ptr or None),
-        ctypes.c_void_p(out_se_ptr or None), ctypes.c_void_p(motion_ptr or None), int(n_obj), ctypes.c_void_p(stream),
-        err, len(err)), err)
+        _vp(rgba_ptr), _vp(se_ptr), _vp(feat_ptr), _vp(prev_mom_ptr), _vp(prev_feat_ptr), _ptr(cam), int(w), int(h),
+        _ref(p), _vp(out_mom_ptr), _vp(out_se_ptr), _vp(motion_ptr), int(n_obj), _vp(stream), err, len(err)), err)

@@ -46,23 +46,29 @@ DEFAULTS = dict(max_history=32, flags=0, normal_cos=0.9, plane_dist=0.02, min_we
 TAPS = ((0, 0), (1, 0), (0, 1), (1, 1))  # (i, j): the tap (x0 + i, y0 + j), in this order
 
 
+def _filled(defaults, params):
+    """`defaults` with the fields that `params` gives -- None, a dict of some fields, or an object with those
+    attributes -- each as its default's type (int or float)."""
+    p = {}
+    for k, d in defaults.items():
+        if isinstance(params, dict):
+            v = params.get(k, d)
+        else:
+            v = getattr(params, k, d)
+        p[k] = type(d)(v)
+    return p
+
+
+def _finite_nonneg(p, *keys):
+    return all(np.isfinite(p[k]) and p[k] >= 0.0 for k in keys)
+
+
 def params_dict(params=None):
     """The parameters as a dict with the defaults filled in (ptmi_reproject_params): from None, a dict
     of some fields, or an object with those attributes (api.ReprojectParams)."""
-    p = dict(DEFAULTS)
-    if params is not None:
-        for k in p:
-            if isinstance(params, dict):
-                if k in params:
-                    p[k] = params[k]
-            elif hasattr(params, k):
-                p[k] = getattr(params, k)
-    p["max_history"], p["flags"] = int(p["max_history"]), int(p["flags"])
-    for k in ("normal_cos", "plane_dist", "min_weight"):
-        p[k] = float(p[k])
-        if not (np.isfinite(p[k]) and p[k] >= 0.0):
-            raise ValueError("bad reproject parameters %r" % (p,))
-    if not 1 <= p["max_history"] <= 65536 or p["flags"] != 0:
+    p = _filled(DEFAULTS, params)
+    if not (_finite_nonneg(p, "normal_cos", "plane_dist", "min_weight") and 1 <= p["max_history"] <= 65536 and
+            p["flags"] == 0):
         raise ValueError("bad reproject parameters %r" % (p,))
     return p
 
@@ -315,18 +321,8 @@ H_RHO = 5  # a rectified history's [5]: rho
 def rectify_params_dict(params=None):
     """The parameters as a dict with the defaults filled in (ptmi_rectify_params): from None, True, a dict
     of some fields, or an object with those attributes (api.RectifyParams)."""
-    p = dict(RECTIFY_DEFAULTS)
-    if params is not None and params is not True:
-        for k in p:
-            if isinstance(params, dict):
-                if k in params:
-                    p[k] = params[k]
-            elif hasattr(params, k):
-                p[k] = getattr(params, k)
-    for k in ("radius", "min_count", "max_history", "flags"):
-        p[k] = int(p[k])
-    p["gamma"] = float(p["gamma"])
-    if not (1 <= p["radius"] <= 4 and 0 <= p["min_count"] < 2 ** 32 and np.isfinite(p["gamma"]) and p["gamma"] >= 0.0 and
+    p = _filled(RECTIFY_DEFAULTS, None if params is True else params)
+    if not (1 <= p["radius"] <= 4 and 0 <= p["min_count"] < 2 ** 32 and _finite_nonneg(p, "gamma") and
             1 <= p["max_history"] <= 65536 and p["flags"] == 0):
         raise ValueError("bad rectify parameters %r" % (p,))
     return p
@@ -417,21 +413,9 @@ VARIANCE_DEFAULTS = dict(max_history=32, min_temporal=4, radius=3, min_count=9, 
 def variance_params_dict(params=None):
     """The parameters as a dict with the defaults filled in (ptmi_variance_params): from None, a dict of some
     fields, or an object with those attributes (api.VarianceParams)."""
-    p = dict(VARIANCE_DEFAULTS)
-    if params is not None:
-        for k in p:
-            if isinstance(params, dict):
-                if k in params:
-                    p[k] = params[k]
-            elif hasattr(params, k):
-                p[k] = getattr(params, k)
-    for k in ("max_history", "min_temporal", "radius", "min_count", "flags"):
-        p[k] = int(p[k])
-    for k in ("normal_cos", "plane_dist", "min_weight", "window_normal_cos"):
-        p[k] = float(p[k])
-        if not (np.isfinite(p[k]) and p[k] >= 0.0):
-            raise ValueError("bad variance parameters %r" % (p,))
-    if not (1 <= p["max_history"] <= 65536 and 2 <= p["min_temporal"] <= 65536 and 1 <= p["radius"] <= 4 and
+    p = _filled(VARIANCE_DEFAULTS, params)
+    if not (_finite_nonneg(p, "normal_cos", "plane_dist", "min_weight", "window_normal_cos") and
+            1 <= p["max_history"] <= 65536 and 2 <= p["min_temporal"] <= 65536 and 1 <= p["radius"] <= 4 and
             2 <= p["min_count"] < 2 ** 32 and p["flags"] == 0):
         raise ValueError("bad variance parameters %r" % (p,))
     return p

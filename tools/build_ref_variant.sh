@@ -11,5 +11,5 @@ for f in $(git ls-tree --name-only $REV include/); do git show $REV:$f > $T/$f; 
 mkdir -p pathtracer-ocl_amd/build/exp
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -Wno-unused-result "$@" \
     -shared -o pathtracer-ocl_amd/build/exp/libptmi_$NAME.so \
-    $T/pathtracer-ocl_amd/csrc/*.hip $T/pathtracer-ocl_amd/csrc/ptmi_api.cpp $T/pathtracer-ocl_amd/csrc/ptmi_bvh.cpp
+    $T/pathtracer-ocl_amd/csrc/*.hip $T/pathtracer-ocl_amd/csrc/*.cpp
 rm -rf $T

@@ -19,7 +19,8 @@ if [ "$NAME" = head ] || [ -n "$FROMREV" ]; then
   git show $REV:pathtracer-ocl_amd/csrc/ptmi_study_kernels.h > $SRC/ptmi_study_kernels.h 2>/dev/null || rm -f $SRC/ptmi_study_kernels.h
   # (the tile classifier, the motion records, the flags / launch / plan headers, the image passes' file: older
   # revisions have none, and keep the image passes in ptmi_kernels.hip)
-  for f in ptmi_camcull.h ptmi_motion.h ptmi_flags.h ptmi_launch.h ptmi_plan.h ptmi_image_kernels.hip; do
+  for f in ptmi_camcull.h ptmi_motion.h ptmi_flags.h ptmi_launch.h ptmi_plan.h ptmi_image_kernels.hip \
+           ptmi_image_api.cpp ptmi_image_args.h ptmi_api_internal.h; do
     git show $REV:pathtracer-ocl_amd/csrc/$f > $SRC/$f 2>/dev/null || rm -f $SRC/$f
   done
   mkdir -p $(dirname $SRC)/../include
@@ -29,4 +30,4 @@ if [ "$NAME" = head ] || [ -n "$FROMREV" ]; then
 fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -Wno-unused-result \
   "$@" -shared -o build/exp/libptmi_$NAME.so $SRC/ptmi_kernels.hip $(ls $SRC/ptmi_image_kernels.hip 2>/dev/null) \
-  $SRC/ptmi_api.cpp $SRC/ptmi_bvh.cpp
+  $SRC/ptmi_api.cpp $(ls $SRC/ptmi_image_api.cpp 2>/dev/null) $SRC/ptmi_bvh.cpp
